@@ -7,14 +7,22 @@ with the gen_syn_data.py distribution generated on device, reference-init parame
 the per-layer L1L1 objective of the training loop fused in, and (N > 1) one RCCL all-reduce of
 the [K, 2] objective sums.  Batch is sharded across ranks: the headline is weak scaling (B per GPU
 fixed); `--global-batch G` makes it strong scaling instead (BASELINE config 3: G = 262,144 columns
-split by dist.shard_columns over the ranks).  The default run also times config 3's strong-scaling
-workload beside the headline (`cfg3_strong`), so every driver run at N = 1/2/4/8 records both
-curves, and at N = 1 configs 2 (B = 10,000), 4 (V6 LASSO 512 x 2048, K = 40) and 5 (bf16,
-1024 x 4096): `cfg2`, `cfg4`, `cfg5`.  The model is built after torch.manual_seed(1126), so the objective is
-reproducible.
+split by dist.shard_columns over the ranks).  The model is built after torch.manual_seed(1126)
+ and the inputs come from seeded generators, so inputs and objective are reproducible.
+
+A plain run does only what the headline needs: set up, W warmup steps, K timed steps, the result
+line.  `--full` adds every secondary measurement to the same line: config 3's strong-scaling
+workload beside the headline (`cfg3_strong`), so a run at N = 1/2/4/8 records both curves; at
+N = 1 configs 2 (B = 10,000), 4 (V6 LASSO 512 x 2048, K = 40) and 5 (bf16, 1024 x 4096): `cfg2`,
+`cfg4`, `cfg5`; the V1 forward (`v1`), the split-f16 legs (`split_f16`), the training step
+(`train`) and the CPU baseline (`cpu_baseline`).  The `--no-*` options drop single legs of a
+`--full` run.  `--dump-outputs DIR` writes what the last timed step returned (a fixed column
+sample of Z, E, L, T; the objective sums) as DIR/<name>.npy, so two builds can be compared
+output for output.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --global-batch G]
-                    [--no-cpu-baseline] [--no-split] [--no-cfg3]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-split] [--no-cfg3]
+                    [--no-train]]
 
 Prints ONE JSON line (rank 0).  Roofline of the dominant kernel (the fused K-layer kernel):
 algorithmic FLOP per launch (4K+2)*m*n*B over its average duration measured here with
@@ -51,9 +59,17 @@ def parse():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: this many columns in total, split over the ranks by "
                          "dist.shard_columns (BASELINE config 3: 262144)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (split-f16 legs, configs 2-5, V1, "
+                         "the training step, the CPU baseline); off by default: a plain run "
+                         "times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy (Z, E, L, T at a fixed seeded sample of columns, fp32; "
+                         "loss_sums and objective, fp64)")
     ap.add_argument("--no-cfg3", action="store_true",
-                    help="skip the secondary measurements of config 3 (strong scaling, 262,144 "
-                         "global columns) and config 2 (B = 10,000, N = 1)")
+                    help="(--full) skip the secondary measurements of config 3 (strong scaling, "
+                         "262,144 global columns) and config 2 (B = 10,000, N = 1)")
     ap.add_argument("--m", type=int, default=256)
     ap.add_argument("--n", type=int, default=512)
     ap.add_argument("--layers", type=int, default=15)
@@ -67,12 +83,14 @@ def parse():
                     help="f32_split = fp32 GEMMs on the f16 matrix cores (exact hi/lo split, 3 "
                          "products, fp32 accumulation); bf16 = BASELINE config 5 mode (bf16 MFMA "
                          "operands, fp32 state): --precision bf16 --m 1024 --n 4096 --batch 16384")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="(--full) skip the CPU baseline")
     ap.add_argument("--no-train", action="store_true",
-                    help="skip the training-step line (SURVEY row f1: V4 forward + fused L1L1 "
-                         "objective + reverse-sweep backward + Adam at the headline shape)")
+                    help="(--full) skip the training-step line (SURVEY row f1: V4 forward + fused "
+                         "L1L1 objective + reverse-sweep backward + Adam at the headline shape)")
     ap.add_argument("--no-split", action="store_true",
-                    help="skip the secondary f32_split measurement of the f32 headline run")
+                    help="(--full) skip the secondary f32_split measurement of the f32 headline "
+                         "run")
     ap.add_argument("--cpu-batch", type=str, default="10000,65536",
                     help="comma-separated batches of the CPU baseline (BASELINE.md: 10,000 and "
                          "65,536)")
@@ -212,6 +230,31 @@ def reduce_timing(elapsed, kern, world, dev, use_dist=None):
     return float(tt[0]), float(tt[1]), [float(x) for x in allk]
 
 
+DUMP_COLS = 256            # columns of the batch that --dump-outputs keeps ...
+DUMP_BYTES = 32 << 20      # ... fewer where the stacked outputs of 256 would exceed this
+
+
+def dump_outputs(dirpath, r, obj, rank):
+    """--dump-outputs: the ForwardResult of the last timed step and its objective as
+    DIR/<name>.npy (rank r > 0: <name>.rank<r>.npy).  Z, E, L, T: every layer written, fp32, at a
+    sorted sample of the rank's columns drawn once from numpy's default_rng(1126) (all columns
+    when the batch is no larger than the sample); loss_sums [K, 2] and objective [K] in fp64."""
+    os.makedirs(dirpath, exist_ok=True)
+    outs = {nm: getattr(r, nm) for nm in ("Z", "E", "L", "T") if getattr(r, nm) is not None}
+    B = r.Z.shape[-1]
+    per_col = sum(4 * t.shape[0] * t.shape[1] for t in outs.values())
+    keep = max(1, min(B, DUMP_COLS, DUMP_BYTES // per_col))
+    cols = np.sort(np.random.default_rng(1126).choice(B, keep, replace=False))
+    idx = torch.from_numpy(cols).to(r.Z.device)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    for nm, t in outs.items():
+        np.save(os.path.join(dirpath, f"{nm}{sfx}.npy"),
+                t.index_select(2, idx).float().cpu().numpy())
+    if r.loss_sums is not None:
+        np.save(os.path.join(dirpath, f"loss_sums{sfx}.npy"), r.loss_sums.double().cpu().numpy())
+        np.save(os.path.join(dirpath, f"objective{sfx}.npy"), obj.double().cpu().numpy())
+
+
 class Workload:
     """One benchmark workload on this rank: the model, its (shard of the) synthetic batch and the
     timed step (forward + the [K, 2] all-reduce)."""
@@ -279,10 +322,11 @@ def main():
         e.record()  # torch creates the hipEvent lazily; make the handles exist
     torch.cuda.synchronize()
 
-    def timed(w, precision):
+    def timed(w, precision, dump=None):
         """W untimed warmup steps, then exactly K timed steps between barrier + synchronize;
         (max-over-ranks wall seconds, max-over-ranks mean kernel seconds, every rank's mean
-        kernel seconds, objective)."""
+        kernel seconds, objective).  dump: the --dump-outputs directory, written after the
+        timed region from the last timed step's result."""
         w.net.precision = precision
         with torch.no_grad():
             for _ in range(a.warmup):
@@ -293,13 +337,19 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
+            last = None
             for i in range(a.steps):
                 r, obj = w.step(keep_all, (ev[2 * i], ev[2 * i + 1]))
+                if dump and i == a.steps - 1:
+                    last = r
                 del r
             torch.cuda.synchronize()
             if use_dist:
                 dist.barrier()
             t1 = time.perf_counter()
+            if last is not None:
+                dump_outputs(dump, last, obj, rank)
+                del last
         elapsed = t1 - t0
         kern = float(np.mean([ev[2 * i].elapsed_time(ev[2 * i + 1])
                               for i in range(a.steps)])) * 1e-3
@@ -308,12 +358,13 @@ def main():
 
     w = make(a.global_batch if strong else 0)
     B = w.B
-    elapsed, kern_avg, kerns, obj = timed(w, a.precision)
+    elapsed, kern_avg, kerns, obj = timed(w, a.precision, a.dump_outputs)
     head_path = w.path
     # the same workload with the fp32 GEMMs on the f16 matrix cores (split-f16, same fp32
     # tolerance tests; tests/test_gpu_split.py), timed the same way beside the headline
     split = None
-    if a.precision == "f32" and m <= 256 and n <= 512 and B % 4 == 0 and not a.no_split:
+    if a.full and a.precision == "f32" and m <= 256 and n <= 512 and B % 4 == 0 and \
+            not a.no_split:
         s_el, s_kern, _, s_obj = timed(w, "f32_split")
         assert w.path == 4, f"split leg ran on path {w.path}, not the split-f16 kernel"
         # untimed: per-layer norm-relative distance of the split path's Z/E/L/T from the fp32
@@ -341,8 +392,9 @@ def main():
     del w
     # BASELINE config 3 (V4, 262,144 columns in total, batch-sharded) beside the weak headline
     cfg3 = None
-    if not strong and not a.no_cfg3 and a.variant == "v4" and a.precision == "f32" and \
-            (m, n, K) == (256, 512, 15):
+    secondary = a.full and not strong and not a.no_cfg3 and a.variant == "v4" and \
+        a.precision == "f32" and (m, n, K) == (256, 512, 15)
+    if secondary:
         w3 = make(262144)
         c_el, c_kern, c_kerns, c_obj = timed(w3, "f32")
         cfg3 = dict(value=262144 * a.steps / c_el, ms_per_step=c_el / a.steps * 1e3,
@@ -351,8 +403,7 @@ def main():
     # BASELINE config 2 (V4, B = 10,000 on one GPU) beside the headline at N = 1: on path 5 (the
     # row-split fused kernel, 625 workgroups of 16 columns)
     cfg2 = None
-    if world == 1 and not strong and not a.no_cfg3 and a.variant == "v4" and \
-            a.precision == "f32" and (m, n, K) == (256, 512, 15) and B != 10000:
+    if world == 1 and secondary and B != 10000:
         w2 = Workload(dl, a, m, n, K, 10000, 10000, None, rank, dev, rank)
         c_el, c_kern, _, c_obj = timed(w2, "f32")
         cfg2 = dict(value=10000 * a.steps / c_el, ms_per_step=c_el / a.steps * 1e3, kern=c_kern,
@@ -364,8 +415,7 @@ def main():
     # BASELINE configs 4 (V6 LASSO m=512 n=2048 K=40, per-layer kernels) and 5 (bf16 operands,
     # m=1024 n=4096 K=15, 16,384 columns = its 131,072 over 8 GPUs) at N = 1
     cfg45 = {}
-    if world == 1 and not strong and not a.no_cfg3 and a.variant == "v4" and \
-            a.precision == "f32" and (m, n, K) == (256, 512, 15):
+    if world == 1 and secondary:
         import copy
         # config 4 at the reference init diverges (V6 at 512 x 2048: the step 0.4 ||A^T A|| ~ 3.6
         # exceeds 2; objective 2.3e27 by layer 40, BENCH_r03): it is timed with the contracting
@@ -385,8 +435,7 @@ def main():
     # the north_star's primary variant V1 (main_lena.py:16-102, DLADMMNet: per-sample (m, B)
     # betas read by every layer) at the headline shape, forward with every layer's Z/E/L written
     v1 = None
-    if world == 1 and not strong and not a.no_cfg3 and a.variant == "v4" and \
-            a.precision == "f32" and (m, n, K) == (256, 512, 15):
+    if world == 1 and secondary:
         import copy
         a1 = copy.copy(a)
         a1.variant = "v1"
@@ -403,7 +452,7 @@ def main():
     # SURVEY row f1 at N = 1: the headline shape's training step (tools/bench_train.py: forward +
     # fused per-layer L1L1 objective + reverse-sweep backward + Adam), timed after everything above
     train = None
-    if world == 1 and not strong and not a.no_train and a.variant == "v4" and \
+    if a.full and world == 1 and not strong and not a.no_train and a.variant == "v4" and \
             a.precision == "f32" and (m, n, K) == (256, 512, 15):
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_train
@@ -636,7 +685,7 @@ def main():
                                     "saved A Z_k, fused L1L1 objective with decay, reverse-sweep "
                                     "backward + split-K weight gradients, torch Adam); backward "
                                     "FLOP = 6 m n K B performed (tools/bench_train.py)")
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(
                 m, n, K, [int(x) for x in a.cpu_batch.split(",") if x], a.cpu_runs, a.variant)
         print(json.dumps(res), flush=True)

@@ -4,8 +4,8 @@
 
 Writes <out>_kernel_stats.csv (copy of the kernel-trace --stats summary), <out>_pmc.json
 (per-launch counter means for the fused kernel) and updates profiles/traffic.json, which bench.py
-reads for roofline.traffic.  bench.py also launches the fused kernel for its config-2 and config-3
-lines, so only launches with the headline's grid (--grid, default 262,144 work-items = B 65,536 /
+reads for roofline.traffic.  bench.py --full also launches the fused kernel for its config-2 and
+config-3 lines, so only launches with the headline's grid (--grid, default 262,144 work-items = B 65,536 /
 16 columns per wave x 64 lanes) are averaged; <out>_headline_stats.csv restates rocprofv3's
 --stats row for those launches alone (its own summary averages every grid of one kernel name).  HBM bytes follow MI355X_MICROARCH.md section HBM: FETCH_SIZE and
 WRITE_SIZE are KiB; on gfx950 FETCH_SIZE reports half of the bytes of WIDE (16 B/lane) coalesced
