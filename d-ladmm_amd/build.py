@@ -26,7 +26,9 @@ UNITS = ("dladmm_capi.hip", "dladmm_fused.hip", "dladmm_fused_savep.hip", "dladm
          "dladmm_reverse_vvar.hip", "dladmm_reverse_v1.hip", "dladmm_reverse_lasso.hip",
          "dladmm_reverse_vvar_small.hip", "dladmm_reverse_v1_small.hip",
          "dladmm_reverse_lasso_small.hip", "dladmm_reverse_v2.hip", "dladmm_reverse_v3.hip",
-         "dladmm_reverse_v2_small.hip", "dladmm_reverse_v3_small.hip")
+         "dladmm_reverse_v2_small.hip", "dladmm_reverse_v3_small.hip",
+         # the row-split sweep's per-row-parameter instantiations (V2 / V3)
+         "dladmm_reverse_rs_v2.hip", "dladmm_reverse_rs_v3.hip")
 INCLUDE = os.path.join(ROOT, "include")
 OUT = os.path.join(HERE, "lib", "libdladmm_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")

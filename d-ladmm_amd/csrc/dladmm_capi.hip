@@ -427,8 +427,12 @@ inline int device_cus() {
                             // 1.08, 8,192 0.72 / 1.10, 10,000 0.94 / 1.12 (3 per CU), 16,384
                             // 1.28 / 1.17 (profiles/r06_rowsplit_ab.json)
 #endif
+// The per-row-parameter variants V2 / V3 take it (and path 6) only under DLADMM_F_ROWSPLIT_ROWP:
+// their default plan stays path 1.
 inline bool use_rowsplit(const dladmm_fwd_desc* d, int shape) {
-  return rs_supports(shape, d->variant) && d->precision == DLADMM_PREC_F32 &&
+  const bool rowv = d->variant == DLADMM_V2_LTHETA || d->variant == DLADMM_V3_FULL;
+  return rs_supports(shape, d->variant) && (!rowv || (d->flags & DLADMM_F_ROWSPLIT_ROWP)) &&
+         d->precision == DLADMM_PREC_F32 &&
          !(d->flags & DLADMM_F_NO_ROWSPLIT) &&
          ceil_div(d->batch, 16) <= DLADMM_RS_PER_CU * device_cus();
 }
@@ -842,6 +846,9 @@ struct BwdPlan {
   // layer (rows padded to Rn2 / Rm2 for the weight gradient), per-wave parameter partials
   bool rev;
   int rtiles, rncg;
+  int rnrow;  // V2 / V3: per-row partial entries per (layer, slot, row): the sweep's waves, or on
+              // the row-split sweeps its 16-column groups (the padding groups of bwd path 3's
+              // grid, which write nothing, are not counted: the reduction never reads them)
   bool rrs;  // reverse sweep on the row-split kernel (16 columns per workgroup)
   bool rxs;  // ... over four workgroups per 16 columns (bwd path 3, after path 6)
   size_t off_rxcnt, off_rxch;  // rxs: hand-off counters (zeroed with the partials), exchange
@@ -979,6 +986,7 @@ inline int make_bwd_plan(const dladmm_bwd_desc* d, BwdPlan* p) {
       p->rtiles = p->rxs ? xs_grid(f.batch)
                   : p->rrs ? ceil_div(f.batch, 16) : ceil_div(f.batch, kTileCols);
       p->rncg = p->rtiles * kWaves;
+      p->rnrow = p->rrs ? ceil_div((int)f.batch, 16) : p->rncg;
     }
   }
   p->wtiles = (int)((p->Rn / 128) * (p->Rm / 128));
@@ -1016,12 +1024,14 @@ inline int make_bwd_plan(const dladmm_bwd_desc* d, BwdPlan* p) {
     p->off_wpart = o; o += align256(lpart * p->wgl);
     p->off_s1dot = o; o += align256(sizeof(double) * (size_t)s1_dot_blocks(n, m) * K);
     p->off_rptab = o; o += align256(sizeof(void*) * (size_t)(RT_NTAB * K + 1));
-    // V2 / V3: per-row partials [K][8][max(MP, NP)][waves] (the kernel's padded rows)
+    // V2 / V3: per-row partials [K][8][max(MP, NP)][rnrow] (the kernel's padded rows).  Never
+    // zeroed: every entry the reduction reads (rows < m / n of the masked slots) is written by the
+    // sweep -- on the row-split sweeps by the one wave of the group that owns the row
     const bool rowk = f.variant == DLADMM_V2_LTHETA || f.variant == DLADMM_V3_FULL;
     p->off_rrow = o;
     const int RS = kShapeMP[p->fwd.shape] > kShapeNP[p->fwd.shape] ? kShapeMP[p->fwd.shape]
                                                                     : kShapeNP[p->fwd.shape];
-    if (rowk) o += align256(sizeof(float) * 8 * K * (size_t)RS * p->rncg);
+    if (rowk) o += align256(sizeof(float) * 8 * K * (size_t)RS * p->rnrow);
     p->off_rxch = o;
     if (p->rxs) o += align256(sizeof(float) * rev_xs_group_floats() * (size_t)(p->rtiles / 4));
     p->total = o;
@@ -1082,6 +1092,7 @@ inline int run_reverse(const dladmm_bwd_desc* d, const BwdPlan& p, char* ws, hip
   RevArgs r{};
   r.m = m; r.n = n; r.B = (int)f.batch; r.K = K;
   r.loss_kind = d->loss_kind; r.ncg = p.rncg;
+  if (f.variant == DLADMM_V2_LTHETA || f.variant == DLADMM_V3_FULL) r.ncg = p.rnrow;
   r.Bw = p.Bpad;
   r.X = f.X; r.ldx = f.ld_x;
   r.E0 = f.E0; r.lde0 = f.ld_e0;
@@ -1171,7 +1182,7 @@ inline int run_reverse(const dladmm_bwd_desc* d, const BwdPlan& p, char* ws, hip
                     (1u << DLADMM_P_BETA2) | (1u << DLADMM_P_THETA_E);
     if (f.variant == DLADMM_V3_FULL) mask |= 1u << DLADMM_P_SS2;
     hipLaunchKernelGGL(row_reduce_kernel, dim3((unsigned)(8 * K * f.row_stride)), dim3(1024), 0,
-                       s, (const float*)r.rpart, p.rncg, MP > NP ? MP : NP, (int)f.row_stride, m,
+                       s, (const float*)r.rpart, p.rnrow, MP > NP ? MP : NP, (int)f.row_stride, m,
                        n, mask, d->g_row);
     if (hipError_t e = hipGetLastError()) return (int)e;
   } else if (f.variant != DLADMM_V1_LENA) {

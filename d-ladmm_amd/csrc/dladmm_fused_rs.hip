@@ -20,7 +20,10 @@
 // wave sums its quarter of the rows, then the 4 quarters in wave order): equal to fp32 rounding.
 // Scope: V1 (per-sample betas), V4, V5 (and the KM iteration built on it), V6 at the 256 x 512
 // register shape; the plan (dladmm_capi.hip) picks it for batches that leave most CUs idle on
-// the fused kernel.
+// the fused kernel.  V2 / V3 (per-row parameters, PK_ROW) run it under DLADMM_F_ROWSPLIT_ROWP:
+// a wave reads the row-table entries of its own rows with each output pair (the 16 lanes of a
+// row on one address), the fused kernel's PK_ROW expressions (Z the clamp form of shrink, E the
+// literal one).
 #include "dladmm_internal.h"
 
 #ifndef RS_PF
@@ -38,6 +41,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   static_assert(NB4 % 2 == 0 && MB4 % 2 == 0, "each wave computes whole pairs of blocks");
   constexpr int S1 = (NB4 / 2) * MB, S2 = (MB4 / 2) * NB;  // MFMA steps of a wave's G1 / G2
   constexpr bool kElem = PKIND == PK_ELEM;  // V1: per-sample betas (m, B) of every layer
+  constexpr bool kRow = PKIND == PK_ROW;    // V2 / V3: per-row parameters [K][8][rstride]
   __shared__ f32x4 zx[NB * 64];  // Z_k of the 16 columns, block b at zx[b * 64 + lane]
   __shared__ f32x4 vx[MB * 64];  // Var
   __shared__ float red[kWaves][2][16];  // per-wave column partials of the fused objective
@@ -88,6 +92,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   struct LayerP { float b1n, b2, b3, ss2, ss2b, s1; ShrinkP the, thz; };
   auto layer_params = [&](int k) -> LayerP {
     LayerP p{};
+    if constexpr (kRow) return p;  // row-table operands (no scalar table)
     const int kk = k < 0 ? 0 : k;
     const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
     cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
@@ -126,6 +131,21 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
           pb[b][2][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rn, (int)vb, (int)so, 0));
         }
     }
+  };
+  // V2 / V3: view of `slot` of layer kk of the row table, bounded to the slot's rows (theta_z: n,
+  // the others: m) -- the padded rows read 0, a finite parameter that meets their all-zero state
+  // (the fused kernel's row_tab_load clamps the row instead; either way they stay zero).  Lane
+  // offset: row 4 g of a block; the block and row go in the uniform offset
+  const uint32_t vr = (uint32_t)(16 * g);
+  auto row_view = [&](int kk, int slot) -> rsrc_t {
+    const int lim = slot == DLADMM_P_THETA_Z ? n : m;
+    return mkrsrc(kRow ? a.rowp + ((int64_t)kk * 8 + slot) * a.rstride : nullptr,
+                  kRow ? (uint32_t)(lim * 4) : 0u);
+  };
+  auto row_ld = [&](rsrc_t r, int b, int rr) -> float {
+    uint32_t o = (uint32_t)(64 * b);
+    asm volatile("" : "+s"(o));
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)vr, (int)(o + 4 * rr), 0));
   };
   // the layer's per-column objective (fused kernel: flush_loss): each wave's quarter of the rows
   // summed over its lane groups, then the 4 quarters in wave order by wave 0 after the barrier
@@ -182,9 +202,17 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
       constexpr int i = decltype(I_)::value;
       if constexpr (i < S1) frag2(rw, I_, fa[i], fb[i]);
     });
+    const rsrc_t rtz = row_view(k, DLADMM_P_THETA_Z);
     static_for<NB4 / 2>([&](auto P_) {
       constexpr int pp = decltype(P_)::value;
       f32x4 ca = zero4, cb = zero4;
+      float tz[2][4];  // V2 / V3: theta_z of the pair's rows, in flight across its products
+      if constexpr (kRow) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) tz[h][r] = row_ld(rtz, b1o + 2 * pp + h, r);
+      }
       static_for<MB>([&](auto J_) {
         constexpr int jb = decltype(J_)::value;
         constexpr int s = pp * MB + jb;
@@ -210,7 +238,9 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float u = (PKIND == PK_S1) ? Zr[lb][r] + P.s1 * q[r] : Zr[lb][r] + q[r];
-          const float z = shrink_u(u, P.thz);
+          float z;
+          if constexpr (kRow) z = shrink_u(u, shrink_params(tz[h][r]));  // the clamp form
+          else z = shrink_u(u, P.thz);
           Zr[lb][r] = z;
           zv[r] = z;
           bstore_s(rzo, vo, row_off(b1o + lb, r), z);
@@ -233,9 +263,29 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
       constexpr int i = decltype(I_)::value;
       if constexpr (i < S2) frag2(ra, I_, fa[i], fb[i]);
     });
+    // V2 / V3: beta2, beta3, theta_e (and V3's ss2) of layer max(k, 0), beta1 of layer k + 1
+    // (the prologue: layer 0; after the last layer it feeds a Var nothing reads: layer K - 1)
+    const int rk = k < 0 ? 0 : k, rkn = k + 1 < K ? k + 1 : rk;
+    const rsrc_t rb2 = row_view(rk, DLADMM_P_BETA2), rb3 = row_view(rk, DLADMM_P_BETA3);
+    const rsrc_t rte = row_view(rk, DLADMM_P_THETA_E), rs2 = row_view(rk, DLADMM_P_SS2);
+    const rsrc_t rb1n = row_view(rkn, DLADMM_P_BETA1);
     static_for<MB4 / 2>([&](auto P_) {
       constexpr int pp = decltype(P_)::value;
       f32x4 ca = zero4, cb = zero4, ca2 = zero4, cb2 = zero4;
+      float rp[2][5][4];  // the pair's row parameters, in flight across its products
+      if constexpr (kRow) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int b = b2o + 2 * pp + h;
+            rp[h][0][r] = row_ld(rb3, b, r);
+            rp[h][1][r] = row_ld(rb2, b, r);
+            rp[h][2][r] = row_ld(rb1n, b, r);
+            rp[h][3][r] = row_ld(rte, b, r);
+            if constexpr (EMODE == EM_VVAR) rp[h][4][r] = row_ld(rs2, b, r);
+          }
+      }
       static_for<NB>([&](auto K_) {
         constexpr int kb = decltype(K_)::value;
         constexpr int s = pp * NB + kb;
@@ -268,16 +318,22 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
             b3 = pb[lb][0][r];
             b2 = pb[lb][1][r];
             b1n = pb[lb][2][r];
+          } else if constexpr (kRow) {
+            b3 = rp[h][0][r];
+            b2 = rp[h][1][r];
+            b1n = rp[h][2][r];
           }
           float e;
           if constexpr (EMODE == EM_V1) {
             // E = S(X - A Z - b2*L, theta_e)                      main_lena.py:87
             const float u = (x - Pv) - b2 * l0;
-            e = shrink_u(u, P.the);
+            if constexpr (kRow) e = shrink(u, rp[h][3][r]);  // per-row theta: the literal form
+            else e = shrink_u(u, P.the);
           } else if constexpr (EMODE == EM_VVAR) {
             // VVar = L + b2*(A Z + E - X); E = S(E - ss2*VVar)    main_syn_l1l1_scalar.py:114-115
             const float vv = l0 + b2 * ((Pv + e0) - x);
-            e = shrink_u(e0 - P.ss2 * vv, P.the);
+            if constexpr (kRow) e = shrink(e0 - rp[h][4][r] * vv, rp[h][3][r]);
+            else e = shrink_u(e0 - P.ss2 * vv, P.the);
           } else {
             // E = ss2_1*(X - A Z) - ss2_2*L                       main_syn_lasso_scalar.py:102-103
             e = P.ss2 * (x - Pv) - P.ss2b * l0;
@@ -337,9 +393,10 @@ hipError_t launch_rs(const FusedArgs& a, int grid, hipStream_t s) {
   return hipGetLastError();
 }
 
+// every variant at the 256 x 512 shape (the plan admits V2 / V3 only under
+// DLADMM_F_ROWSPLIT_ROWP: dladmm_capi.hip use_rowsplit)
 bool rs_supports(int shape, int variant) {
-  return shape == 2 && (variant == DLADMM_V1_LENA || variant == DLADMM_V4_SCALAR ||
-                        variant == DLADMM_V5_TIED || variant == DLADMM_V6_LASSO);
+  return shape == 2 && variant >= DLADMM_V1_LENA && variant <= DLADMM_V6_LASSO;
 }
 
 hipError_t launch_fused_rs(int shape, int variant, const FusedArgs& a, int grid, hipStream_t s) {
@@ -347,6 +404,8 @@ hipError_t launch_fused_rs(int shape, int variant, const FusedArgs& a, int grid,
   constexpr int MP = kShapeMP[2], NP = kShapeNP[2];
   switch (variant) {
     case DLADMM_V1_LENA: return launch_rs<MP, NP, EM_V1, PK_ELEM>(a, grid, s);
+    case DLADMM_V2_LTHETA: return launch_rs<MP, NP, EM_V1, PK_ROW>(a, grid, s);
+    case DLADMM_V3_FULL: return launch_rs<MP, NP, EM_VVAR, PK_ROW>(a, grid, s);
     case DLADMM_V4_SCALAR: return launch_rs<MP, NP, EM_VVAR, PK_SCALAR>(a, grid, s);
     case DLADMM_V5_TIED: return launch_rs<MP, NP, EM_VVAR, PK_S1>(a, grid, s);
     case DLADMM_V6_LASSO: return launch_rs<MP, NP, EM_LASSO, PK_SCALAR>(a, grid, s);

@@ -24,9 +24,11 @@
 //
 // Arithmetic is path 5's, operation for operation (the same packed fragments, G1 one chain per
 // block over k in order, G2 the two chains summed once, the same elementwise expressions): the
-// outputs are the fused kernel's bit for bit (tests/test_gpu_xsplit.py).  The per-column
+// outputs are the fused kernel's bit for bit (tests/test_gpu_rowsplit.py).  The per-column
 // objective sums its 16 wave partials in wave order: equal to fp32 rounding.
-// Scope: V1, V4, V5, V6 at the 256 x 512 register shape, fp32.
+// Scope: V1, V4, V5, V6 at the 256 x 512 register shape, fp32; V2 / V3 (per-row parameters,
+// PK_ROW) under DLADMM_F_ROWSPLIT_ROWP, each wave reading the row-table entries of its own rows
+// at the start of a pass (tests/test_gpu_rowsplit_rowp.py).
 #include "dladmm_internal.h"
 
 #ifndef XS_PF
@@ -59,6 +61,7 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
   static_assert(NB == 2 * kXsWaves && MB == kXsWaves, "one G1 pair and one G2 block per wave");
   constexpr int S1 = MB, S2 = NB;  // MFMA steps of a wave's G1 / G2
   constexpr bool kElem = PKIND == PK_ELEM;
+  constexpr bool kRow = PKIND == PK_ROW;  // V2 / V3: per-row parameters [K][8][rstride]
   __shared__ f32x4 zx[NB * 64];  // Z_k of the 16 columns, block b at zx[b * 64 + lane]
   __shared__ f32x4 vx[MB * 64];  // Var
 
@@ -164,6 +167,7 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
   struct LayerP { float b1n, b2, b3, ss2, ss2b, s1; ShrinkP the, thz; };
   auto layer_params = [&](int k) -> LayerP {
     LayerP p{};
+    if constexpr (kRow) return p;  // row-table operands (no scalar table)
     const int kk = k < 0 ? 0 : k;
     const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
     cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
@@ -198,6 +202,18 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
         pb[2][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rn, (int)vb, (int)so, 0));
       }
     }
+  };
+  // V2 / V3: view of `slot` of layer kk of the row table, bounded to the slot's rows (theta_z: n,
+  // the others: m): the padded rows read 0, a finite parameter that meets their all-zero state.
+  // Lane offset: row 4 g of a block; the block and row go in the uniform offset
+  const uint32_t vr = (uint32_t)(16 * g);
+  auto row_view = [&](int kk, int slot) -> rsrc_t {
+    const int lim = slot == DLADMM_P_THETA_Z ? n : m;
+    return mkrsrc(kRow ? a.rowp + ((int64_t)kk * 8 + slot) * a.rstride : nullptr,
+                  kRow ? (uint32_t)(lim * 4) : 0u);
+  };
+  auto row_ld = [&](rsrc_t r, int b, int rr) -> float {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)vr, 64 * b + 4 * rr, 0));
   };
   // the layer's per-column objective: this wave's partial to the exchange buffer (handed off with
   // the Var blocks), summed over the 16 waves in order by member 0's wave 0 after that hand-off
@@ -261,6 +277,14 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
   auto g1_pass = [&](int k, const LayerP& P, rsrc_t rzo) {
     const rsrc_t rw = rw_of(k);
     f32x4 ca = zero4, cb = zero4;
+    float tz[2][4];  // V2 / V3: theta_z of this wave's rows, in flight across the products
+    if constexpr (kRow) {
+      const rsrc_t rtz = row_view(k, DLADMM_P_THETA_Z);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tz[h][r] = row_ld(rtz, b1o + h, r);
+    }
     static_for<S1>([&](auto J_) {
       constexpr int s = decltype(J_)::value;
       const f32x4 vv = vx[s * 64 + lane];
@@ -285,7 +309,9 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float u = (PKIND == PK_S1) ? Zr[h][r] + P.s1 * q[r] : Zr[h][r] + q[r];
-        const float z = shrink_u(u, P.thz);
+        float z;
+        if constexpr (kRow) z = shrink_u(u, shrink_params(tz[h][r]));  // the clamp form
+        else z = shrink_u(u, P.thz);
         Zr[h][r] = z;
         zv[r] = z;
         bstore_s(rzo, vo, row_off(b1o + h, r), fin(z));
@@ -309,6 +335,23 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
   auto g2_pass = [&](auto PRO_, int k, const LayerP& P, const OutR& O) {
     constexpr bool PRO = decltype(PRO_)::value;
     load_betas(k);
+    // V2 / V3: beta3, beta2, theta_e (and V3's ss2) of layer max(k, 0), beta1 of layer k + 1 (the
+    // prologue: layer 0; after the last layer it feeds a Var nothing reads: layer K - 1)
+    float rp[5][4];
+    if constexpr (kRow) {
+      const int rk = k < 0 ? 0 : k, rkn = k + 1 < K ? k + 1 : rk;
+      const rsrc_t rb2 = row_view(rk, DLADMM_P_BETA2), rb3 = row_view(rk, DLADMM_P_BETA3);
+      const rsrc_t rte = row_view(rk, DLADMM_P_THETA_E), rs2 = row_view(rk, DLADMM_P_SS2);
+      const rsrc_t rb1n = row_view(rkn, DLADMM_P_BETA1);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        rp[0][r] = row_ld(rb3, b2o, r);
+        rp[1][r] = row_ld(rb2, b2o, r);
+        rp[2][r] = row_ld(rb1n, b2o, r);
+        rp[3][r] = row_ld(rte, b2o, r);
+        if constexpr (EMODE == EM_VVAR) rp[4][r] = row_ld(rs2, b2o, r);
+      }
+    }
     f32x4 ca = zero4, ca2 = zero4;
     static_for<S2>([&](auto K_) {
       constexpr int s = decltype(K_)::value;
@@ -331,14 +374,20 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
         b3 = pb[0][r];
         b2 = pb[1][r];
         b1n = pb[2][r];
+      } else if constexpr (kRow) {
+        b3 = rp[0][r];
+        b2 = rp[1][r];
+        b1n = rp[2][r];
       }
       float e;
       if constexpr (EMODE == EM_V1) {
         const float u = (x - Pv) - b2 * l0;            // main_lena.py:87
-        e = shrink_u(u, P.the);
+        if constexpr (kRow) e = shrink(u, rp[3][r]);   // per-row theta: the literal form
+        else e = shrink_u(u, P.the);
       } else if constexpr (EMODE == EM_VVAR) {
         const float vv = l0 + b2 * ((Pv + e0) - x);    // main_syn_l1l1_scalar.py:114-115
-        e = shrink_u(e0 - P.ss2 * vv, P.the);
+        if constexpr (kRow) e = shrink(e0 - rp[4][r] * vv, rp[3][r]);
+        else e = shrink_u(e0 - P.ss2 * vv, P.the);
       } else {
         e = P.ss2 * (x - Pv) - P.ss2b * l0;            // main_syn_lasso_scalar.py:102-103
       }
@@ -413,6 +462,8 @@ hipError_t launch_fused_xs(int shape, int variant, const FusedArgs& a, hipStream
   const int grid = xs_grid(a.B);
   switch (variant) {
     case DLADMM_V1_LENA: return launch_xs<MP, NP, EM_V1, PK_ELEM>(a, grid, s);
+    case DLADMM_V2_LTHETA: return launch_xs<MP, NP, EM_V1, PK_ROW>(a, grid, s);
+    case DLADMM_V3_FULL: return launch_xs<MP, NP, EM_VVAR, PK_ROW>(a, grid, s);
     case DLADMM_V4_SCALAR: return launch_xs<MP, NP, EM_VVAR, PK_SCALAR>(a, grid, s);
     case DLADMM_V5_TIED: return launch_xs<MP, NP, EM_VVAR, PK_S1>(a, grid, s);
     case DLADMM_V6_LASSO: return launch_xs<MP, NP, EM_LASSO, PK_SCALAR>(a, grid, s);

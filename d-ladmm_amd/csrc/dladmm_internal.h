@@ -212,7 +212,8 @@ __host__ __device__ constexpr int rev_tab_at(int tab, int K, int k) {
 }
 struct RevArgs {
   int m, n, B, K;
-  int loss_kind, ncg;              // ncg: waves (column groups) = partial entries per slot
+  int loss_kind, ncg;              // ncg: partial entries per slot: waves (column groups); V2 / V3
+                                   // on the row-split sweeps: 16-column groups (rpart's last axis)
   int64_t Bw;                      // padded batch of the gU / Var workspaces (stored as zeros)
   const float* X; int64_t ldx;
   const float* E0; int64_t lde0;
@@ -232,7 +233,7 @@ struct RevArgs {
   const float* const* ptab;        // RevTab pointer table (device)
   int has_gz, has_cot;             // cotangents of Z; of E / L / T
   const float* rowp; int64_t rstride;  // V2 / V3: per-row parameter table [K][8][rstride]
-  float* rpart;                    // V2 / V3: per-row partials [K][8][rstride][ncg]
+  float* rpart;                    // V2 / V3: per-row partials [K][8][max(MP, NP)][ncg]
   // the four-workgroup row split (bwd path 3): per-group exchange buffers (xstride floats each)
   // and hand-off counters (64 per group, zeroed before the launch)
   float* xch; int64_t xstride; unsigned* xcnt;
@@ -241,8 +242,8 @@ static_assert(sizeof(RevArgs) <= 2048, "kernel argument size");
 bool reverse_supports(int variant);
 hipError_t launch_reverse_shape(int shape, int variant, const RevArgs& a, int grid, hipStream_t s);
 // the small-batch row-split reverse sweep (dladmm_reverse_rs.hip): 16 columns per workgroup,
-// grid = ceil(B / 16), after a path-5 forward; V4 / V5 / V6 at the 256 x 512 shape, no E / L / T
-// cotangents
+// grid = ceil(B / 16), after a path-5 forward; every variant at the 256 x 512 shape (V2 / V3 reach
+// it only through DLADMM_F_ROWSPLIT_ROWP, which the forward plan gates)
 bool reverse_rs_supports(int shape, int variant);
 hipError_t launch_reverse_rs(int shape, int variant, const RevArgs& a, int grid, hipStream_t s);
 // its four-workgroup form (bwd path 3, after path 6): grid xs_grid(B), exchange a.xch / a.xcnt

@@ -159,7 +159,7 @@ typedef struct dladmm_fwd_desc {
   int32_t flags;
 
   /* optional (training): P [K][m][ld_out] receives A Z_k of every layer, exactly the product the
-     E/L/T updates consumed (main_syn_l1l1_scalar.py:114-117).  Written only on paths 1, 4 and 5
+     E/L/T updates consumed (main_syn_l1l1_scalar.py:114-117).  Written only on paths 1, 4, 5 and 6
      (fused kernels, keep_all = 1; dladmm_fwd_path() tells); ignored on every other path.  A backward
      whose fwd.P is set reads it instead of recomputing the product (one GEMM per layer less). */
   float* P;
@@ -183,8 +183,12 @@ enum dladmm_flags {
   DLADMM_F_NO_ROWSPLIT = 64,   /* forward: the fused kernel (path 1) where the small-batch
                                   row-split kernels (paths 5 / 6) would run (equivalence tests,
                                   A/B)                                                             */
-  DLADMM_F_NO_XSPLIT = 128     /* forward: the one-workgroup row split (path 5) where the
+  DLADMM_F_NO_XSPLIT = 128,    /* forward: the one-workgroup row split (path 5) where the
                                   four-workgroup one (path 6) would run                            */
+  DLADMM_F_ROWSPLIT_ROWP = 256 /* forward: the row-split forms (paths 5 / 6) also for the
+                                  per-row-parameter variants V2 / V3, which keep path 1 without
+                                  it; the backward follows the forward as for the other variants
+                                  (dladmm_bwd_path 2 / 3).  No effect on any other variant         */
 };
 
 /* ABI version the library was built with. */
@@ -197,8 +201,8 @@ size_t dladmm_fwd_workspace_bytes(const dladmm_fwd_desc* d);
    2 = per-layer kernel pair (large shapes, or one layer's matrix >= 2^31 bytes), 3 = per-layer
    tile kernels on bf16 operands, 4 = fused kernel on split-f16 operands (DLADMM_PREC_F32_SPLIT),
    5 = fused kernel with each workgroup's rows split over its waves (16 columns per workgroup):
-   small fp32 batches (at most three workgroups per CU) of V1 / V4 / V5 / V6 at m <= 256,
-   n <= 512 (and m > 64 or n > 256) -- the same arithmetic as path 1, bit for bit (the fused
+   small fp32 batches (at most three workgroups per CU) of V1 / V4 / V5 / V6 (V2 / V3 under
+   DLADMM_F_ROWSPLIT_ROWP) at m <= 256, n <= 512 (and m > 64 or n > 256) -- the same arithmetic as path 1, bit for bit (the fused
    objective's per-column sums: to fp32 rounding), 6 = the same split over four workgroups per
    16 columns (16 waves; the column state handed between them through the workspace once per
    product) where that grid fits one workgroup per CU (B <= 1,024 on 256 CUs), also bit for bit;
@@ -274,7 +278,8 @@ size_t dladmm_bwd_workspace_bytes(const dladmm_bwd_desc* d);
 
 /* Which kernels the backward runs: 1 = one reverse-sweep kernel for every layer's adjoints,
    2 = the same sweep in its small-batch row-split form (16 columns per workgroup, each
-   product's rows over its waves; after an fp32 path-5 / 6 forward of V1 / V4 / V5 / V6, any
+   product's rows over its waves; after an fp32 path-5 / 6 forward of V1 / V4 / V5 / V6, or of V2 / V3 under
+   DLADMM_F_ROWSPLIT_ROWP (per-row gradients: the 64-column sweep's partials and order), any
    cotangents, at most one 16-column workgroup per CU: gU_k, Var_k, the weight gradients and
    V1's beta gradients bit-equal to path 1's, the scalar-parameter gradients to rounding),
    3 = that form over four workgroups per 16 columns after a path-6 forward (the same

@@ -30,6 +30,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--layers", type=int, default=15)
+    ap.add_argument("--variant", default="v4", choices=["v2", "v3", "v4"],
+                    help="model variant; v2 / v3 (per-row parameters) reach bwd paths 3 / 2 with "
+                         "the forward plan flag rowsplit_rows (256), e.g. --flag-set 256,384,0")
     ap.add_argument("--gz", action="store_true",
                     help="per-layer Z cotangents (a loss built from the returned Z_k with torch "
                          "ops, the reference's training loops) instead of the fused objective")
@@ -40,7 +43,8 @@ def main():
                     help="plan flag bwd_per_layer: the per-layer backward kernels")
     ap.add_argument("--flag-set", default="",
                     help="comma-separated forward plan flags to compare with the in-tree library "
-                         "(e.g. 0,128,64: bwd paths 3 / 2 / 1 at small batches); overrides --libs")
+                         "(e.g. 0,128,64: bwd paths 3 / 2 / 1 at small batches; V2 / V3: 256,384,0); "
+                         "overrides --libs")
     a = ap.parse_args()
     dl = importlib.import_module("d-ladmm_amd")
     ops = importlib.import_module("d-ladmm_amd.ops")
@@ -49,7 +53,7 @@ def main():
     m, n, K, B = 256, 512, a.layers, a.batch
     torch.manual_seed(1126)
     A, X, Z0, E0, L0 = bench.synth(m, n, B, 0, dev)
-    net = dl.DLADMMNetScalar(m=m, n=0, d=n, batch_size=B, A=A, Z0=Z0, E0=E0, L0=L0, layers=K)
+    net = dl.VARIANTS[a.variant](m=m, n=0, d=n, batch_size=B, A=A, Z0=Z0, E0=E0, L0=L0, layers=K)
     net.cuda()
     with torch.no_grad():
         tables = net._tables(dev)
@@ -94,7 +98,7 @@ def main():
             del res
     out = {s: {"median_ms": float(np.median(t)), "min_ms": float(np.min(t)), "bwd_path": paths[s]}
            for s, t in times.items()}
-    out["config"] = dict(m=m, n=n, K=K, B=B, reps=a.reps, rev=not a.per_layer, gz=a.gz,
+    out["config"] = dict(variant=a.variant, m=m, n=n, K=K, B=B, reps=a.reps, rev=not a.per_layer, gz=a.gz,
                          no_rowsplit=a.no_rowsplit, bwd_path=bwd_path)
     print(json.dumps(out))
 

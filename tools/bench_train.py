@@ -57,6 +57,10 @@ def parser():
                     help="also time the whole step (zero_grad, forward, loss, backward, Adam with "
                          "capturable=True) captured once as a HIP graph and replayed (torch's "
                          "whole-network recipe): the step without the Python / launch overhead")
+    ap.add_argument("--plan-flags", default="",
+                    help="comma-separated plan options (d-ladmm_amd.ops.plan_flags names) for every "
+                         "forward and backward of the run, e.g. rowsplit_rows: V2 / V3 on the "
+                         "small-batch row-split kernels")
     ap.add_argument("--fused-loss", action="store_true",
                     help="net.training_loss (objective fused into the kernels) instead of the "
                          "reference's torch-op loss over the returned Z_k")
@@ -65,6 +69,14 @@ def parser():
 
 def run(a) -> dict:
     """One training-step measurement (the parsed options of parser()); returns the JSON dict."""
+    names = [f for f in getattr(a, "plan_flags", "").split(",") if f]
+    if names:  # the options hold for every call of the run (a backward keeps its forward's)
+        ops = importlib.import_module("d-ladmm_amd.ops")
+        with ops.plan_flags(**{f: True for f in names}):
+            a2 = argparse.Namespace(**{**vars(a), "plan_flags": ""})
+            res = run(a2)
+        res["plan_flags"] = names
+        return res
     dl = importlib.import_module("d-ladmm_amd")
     dev = torch.device("cuda", 0)
     m, n, K, B = a.m, a.n, a.layers, a.batch
