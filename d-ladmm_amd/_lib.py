@@ -23,6 +23,8 @@ F_PER_LAYER, F_BF16_WIDE, F_BWD_PER_LAYER, F_BWD_UNFUSED, F_BWD_NO_ZMASK, F_WGRA
 F_NO_ROWSPLIT = 64
 F_NO_XSPLIT = 128
 F_ROWSPLIT_ROWP = 256
+F_P0_SAVE = 512      # path 1, fp32: also leave the packed A and P0 = A Z0 in the workspace
+F_P0_REUSE = 1024    # path 1, fp32: read them from the workspace a F_P0_SAVE call ran on
 # enum dladmm_variant
 V1_LENA, V2_LTHETA, V3_FULL, V4_SCALAR, V5_TIED, V6_LASSO = 1, 2, 3, 4, 5, 6
 # enum dladmm_loss_kind

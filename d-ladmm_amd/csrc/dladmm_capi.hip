@@ -337,6 +337,8 @@ struct Plan {
   size_t off_btab;            // path 1, V1: device tables of the per-layer beta pointers
   size_t off_xch, off_xcnt;   // path 6: exchange buffers, hand-off counters
   size_t off_wexp, off_umax;  // path 4
+  bool p0;                    // path 1: DLADMM_F_P0_SAVE / DLADMM_F_P0_REUSE act (P0 region reserved)
+  size_t off_p0;              // the saved prologue product A Z0, [MP][ldl] floats
   int64_t ldzw;               // path 4: lean-mode Z_k workspace row stride
 };
 
@@ -495,6 +497,16 @@ inline int make_plan(const dladmm_fwd_desc* d, Plan* p) {
     p->off_btab = p->off_loss + align256((size_t)2 * K * p->nslots * sizeof(float));
     p->total = p->off_btab +
                (d->variant == DLADMM_V1_LENA ? align256((size_t)2 * K * sizeof(void*)) : 0);
+    // reuse of the prologue product (DLADMM_F_P0_SAVE / DLADMM_F_P0_REUSE): path 1, fp32 proper;
+    // the region goes after every existing one, so their offsets stay (the load form addresses it
+    // with 32-bit buffer offsets)
+    if (p->path == 1 && (d->flags & (DLADMM_F_P0_SAVE | DLADMM_F_P0_REUSE)) &&
+        d->precision == DLADMM_PREC_F32 && p0_supports(s, d->variant) &&
+        (int64_t)p->MP * p->ldl * 4 < ((int64_t)1 << 31)) {
+      p->p0 = true;
+      p->off_p0 = p->total;
+      p->total += align256((size_t)p->MP * p->ldl * sizeof(float));
+    }
     if (p->path == 6) {  // exchange buffers and hand-off counters of every (padded) group
       const size_t groups = (size_t)xs_grid(d->batch) / 4;
       p->off_xch = p->total;
@@ -584,7 +596,11 @@ inline int run_fused(const dladmm_fwd_desc* d, const Plan& p, char* ws, hipStrea
   //    shared by every layer is packed once
   const float* asrc[1] = {d->A};
   const bool shared = shared_weight(d);
-  if (hipError_t e = pack(asrc, 1, d->m, d->n, d->ld_a, MB, NB, 2, Ap, s)) return (int)e;
+  // DLADMM_F_P0_REUSE: the packed A and P0 = A Z0 are those an earlier DLADMM_F_P0_SAVE call left
+  // in this workspace (the caller's contract, include/dladmm.h)
+  const bool p0_reuse = p.p0 && !(d->flags & DLADMM_F_P0_SAVE);
+  if (!p0_reuse)
+    if (hipError_t e = pack(asrc, 1, d->m, d->n, d->ld_a, MB, NB, 2, Ap, s)) return (int)e;
   if (hipError_t e = pack(d->W, shared ? 1 : d->layers, d->n, d->m, d->ld_w, NB, MB, 2, Wp, s,
                           -1.0f))
     return (int)e;
@@ -621,6 +637,14 @@ inline int run_fused(const dladmm_fwd_desc* d, const Plan& p, char* ws, hipStrea
   // training forwards also store P_k = A Z_k for the backward (fwd_desc.P, keep_all only)
   const bool savep = d->P != nullptr && d->keep_all;
   a.Po = savep ? d->P : nullptr;
+  if (p.p0) {
+    a.P0 = (const float*)(ws + p.off_p0);
+    a.ldp0 = p.ldl;
+    if (!p0_reuse)  // DLADMM_F_P0_SAVE: the product the compute form is about to form, bit for bit
+      if (hipError_t e = launch_p0_producer(p.shape, Ap, d->Z0, d->ld_z0, d->n, d->batch,
+                                            (float*)(ws + p.off_p0), p.ldl, p.tiles, s))
+        return (int)e;
+  }
   if (d->ev_kernel_start) {
     if (hipError_t e = hipEventRecord((hipEvent_t)d->ev_kernel_start, s)) return (int)e;
   }
@@ -633,6 +657,9 @@ inline int run_fused(const dladmm_fwd_desc* d, const Plan& p, char* ws, hipStrea
   hipError_t e = p.path == 6 ? launch_fused_xs(p.shape, d->variant, a, s)
                  : p.path == 5
                     ? launch_fused_rs(p.shape, d->variant, a, ceil_div(d->batch, 16), s)
+                 : p0_reuse
+                    ? (savep ? launch_fused_shape_p0_savep : launch_fused_shape_p0)(
+                          p.shape, d->variant, a, p.tiles, s)
                     : (savep ? launch_fused_shape_savep : launch_fused_shape)(p.shape, d->variant,
                                                                              a, p.tiles, s);
   if (e) return (int)e;

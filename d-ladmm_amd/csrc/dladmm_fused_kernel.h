@@ -168,7 +168,13 @@ struct WinCount {
 
 // SAVEP: also store P_k = A Z_k (a.Po) for the backward's BK1 (training forwards only: the
 // fourth store per G2 element costs the inference path about 1.5 %)
-template <int MP, int NP, int EMODE, int PKIND, bool SAVEP>
+// P0LOAD: the "load P0" form.  A Z0 does not depend on the layers, so a caller that keeps A and
+// Z0 from call to call (include/dladmm.h, DLADMM_F_P0_REUSE) passes the product saved by an earlier
+// call (a.P0, written by p0_kernel with this kernel's own MFMA sequence: the same bits).  The
+// prologue GEMM pass is not run: the ring stream starts at W_0, the prologue's epilogue rows run
+// up front from the loaded product, and the last pair's product goes to qa / qb so that G1(0)
+// runs its rows as in the compute form.  Everything from G1(0) on is the compute form's code.
+template <int MP, int NP, int EMODE, int PKIND, bool SAVEP, bool P0LOAD = false>
 __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   using F = Fused<MP, NP, EMODE, PKIND>;
   constexpr int MB = F::MB, NB = F::NB, CF = F::CF, NCH = F::NCH, TAB = F::TAB;
@@ -301,13 +307,20 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
     const uint32_t oz = lane_off(a.ldz0), oe = lane_off(a.lde0),
                    ol = lane_off(a.ldl0), ox = lane_off(a.ldx);
     const rsrc_t rx = mkrsrc(a.X, (uint32_t)(m * a.ldx * 4));
+    if constexpr (P0LOAD) {
+      // the ring priming depends on nothing: first.  Z0 is loaded after the priming barrier
+      // (below), so that the barrier's vmcnt(0) does not wait for it.
 #pragma unroll
-    for (int b = 0; b < NB; ++b)
+      for (int c = 0; c < F::SLOTS - 1; ++c) issue(chunk_src(1, c), c);
+    } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        Zr[b][r] = bload(rz, oz + (uint32_t)((16 * b + r) * a.ldz0 * 4));
-        pin_agpr(Zr[b][r]);
-      }
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          Zr[b][r] = bload(rz, oz + (uint32_t)((16 * b + r) * a.ldz0 * 4));
+          pin_agpr(Zr[b][r]);
+        }
+    }
 #pragma unroll
     for (int b = 0; b < MB; ++b) {
       f32x4 xv;
@@ -323,6 +336,19 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
     }
   }
   row_tab_load(0, 0);
+  // P0LOAD: the saved A Z0 of every output block, [MP][ldp0] like X; in flight beside the ring
+  // priming and the state loads, all waited for by the priming barrier.  Temporaries: dead after
+  // the up-front rows.
+  f32x4 p0q[P0LOAD ? MB : 1];
+  if constexpr (P0LOAD) {
+    const rsrc_t rp = mkrsrc(a.P0, (uint32_t)(MP * a.ldp0 * 4));
+    const uint32_t op = lane_off(a.ldp0);
+#pragma unroll
+    for (int b = 0; b < MB; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        p0q[b][r] = bload(rp, op + (uint32_t)((16 * b + r) * a.ldp0 * 4));
+  }
 
   const uint32_t vo = lane_off(a.ldo);  // output lane offset (voffset of every store)
   const uint32_t vb = lane_off(a.ldb);  // per-element beta lane offset
@@ -573,11 +599,18 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   };
 
   // prime the ring: the first SLOTS - 1 chunks, then the first step's fragments
+  if constexpr (!P0LOAD) {
 #pragma unroll
-  for (int c = 0; c < F::SLOTS - 1; ++c) issue(chunk_src(0, c), c);
+    for (int c = 0; c < F::SLOTS - 1; ++c) issue(chunk_src(0, c), c);
+  }
   ring_barrier();
   fr[0] = frag(0, 0);
   fr[1] = frag(0, 1);
+#if DLADMM_STAMP
+  __builtin_amdgcn_sched_barrier(0);
+  const uint64_t st_primed = stamp();  // state loads and ring priming have landed
+  __builtin_amdgcn_sched_barrier(0);
+#endif
 
   // ---------------------------------------------------------------- the GEMM passes
   f32x4 qa = {0.f, 0.f, 0.f, 0.f}, qb = {0.f, 0.f, 0.f, 0.f};  // pending pair accumulators
@@ -709,7 +742,55 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   LayerP Pp = layer_params(-1);
   OutR Op{none, none,
           mkrsrc(a.keep_all ? a.To : nullptr, (a.keep_all && a.To) ? mbytes : 0u), none};
-  g2_pass(std::true_type{}, -1, Pp, Op, none);
+  if constexpr (P0LOAD) {
+    // after the priming barrier: layer 0's row table (PK_ROW) has landed for every wave
+    {
+      const rsrc_t rz = mkrsrc(a.Z0, (uint32_t)(n * a.ldz0 * 4));
+      const uint32_t oz = lane_off(a.ldz0);
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          Zr[b][r] = bload(rz, oz + (uint32_t)((16 * b + r) * a.ldz0 * 4));
+          pin_agpr(Zr[b][r]);
+        }
+    }
+    // the prologue's rows of blocks 0 .. MB-3 (epi2_row's pro form: T0 store, Var_0, 0-record
+    // E / L stores); the last pair's product goes to qa / qb: G1(0) pair 0 runs its rows.
+    // PK_ELEM: E0 (V1 keeps no E state) and layer 0's beta1 come straight from memory into the
+    // slots the row reads; the last pair's stay there for G1(0).
+    mw.reset();
+    beta_ptrs(-1);
+    static_for<MB>([&](auto B_) {
+      constexpr int b = decltype(B_)::value, h = b % 2;
+      if constexpr (PKIND == PK_ELEM) {
+        const rsrc_t re = mkrsrc(a.E0, (uint32_t)(m * a.lde0 * 4));
+        const rsrc_t rb = mkrsrc(bpn, (uint32_t)(m * a.ldb * 4));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          pb[h][0][r] = 0.f;
+          pb[h][1][r] = bload(re, ve + (uint32_t)((16 * b + r) * a.lde0 * 4));
+          pb[h][2][r] = bload(rb, vb + (uint32_t)((16 * b + r) * a.ldb * 4));
+        }
+      }
+      if constexpr (b < MB - 2) {
+        const f32x4 xv = xs[(w * MB + b) * 64 + lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) epi2_row(Pp, Op, -1, true, b, h, r, p0q[b], xv);
+      } else if constexpr (h == 0) {
+        qa = p0q[b];
+      } else {
+        qb = p0q[b];
+      }
+    });
+  } else {
+    g2_pass(std::true_type{}, -1, Pp, Op, none);
+  }
+#if DLADMM_STAMP
+  __builtin_amdgcn_sched_barrier(0);
+  const uint64_t st_pro = stamp();  // the prologue pass, or the load form's up-front rows
+  __builtin_amdgcn_sched_barrier(0);
+#endif
   for (int k = 0; k < K; ++k) {
     const bool st = a.keep_all || k == K - 1;
     const int ko = a.keep_all ? k : 0;
@@ -755,7 +836,8 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
 #if DLADMM_STAMP
   const uint64_t st_end = stamp();
   if (a.dbg && lane < 8) {  // vector stores: lane i writes sum i
-    const uint64_t v[8] = {st_end - st_0, st_g1, st_g2, 0, st_vm, st_bar, 0, 0};
+    const uint64_t v[8] = {st_end - st_0, st_g1, st_g2, 0, st_vm, st_bar, st_primed - st_0,
+                           st_pro - st_primed};
     uint64_t x = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) x = lane == i ? v[i] : x;
@@ -765,9 +847,10 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
 }
 
 
-template <int MP, int NP, int EM, int PK, bool SAVEP>
+template <int MP, int NP, int EM, int PK, bool SAVEP, bool P0LOAD = false>
 hipError_t launch_fused(const FusedArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((fused_kernel<MP, NP, EM, PK, SAVEP>), dim3(grid), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((fused_kernel<MP, NP, EM, PK, SAVEP, P0LOAD>), dim3(grid), dim3(256), 0, s,
+                     a);
   return hipGetLastError();
 }
 

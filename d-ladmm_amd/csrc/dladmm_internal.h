@@ -39,6 +39,8 @@ struct FusedArgs {
   // counters (64 per group, zeroed before the launch)
   float* xch; int64_t xstride;
   unsigned* xcnt;
+  // the load-P0 form (dladmm_fused_p0.hip): the saved prologue product A Z0, [MP][ldp0]
+  const float* P0; int64_t ldp0;
 };
 
 
@@ -52,6 +54,18 @@ hipError_t launch_fused_shape(int shape, int variant, const FusedArgs& a, int gr
 // the same kernels that also store P_k = A Z_k (a.Po) for the backward (dladmm_fused_savep.hip)
 hipError_t launch_fused_shape_savep(int shape, int variant, const FusedArgs& a, int grid,
                                     hipStream_t s);
+// the load-P0 form of the same kernels (dladmm_fused_p0.hip, dladmm_fused_p0_savep.hip): no
+// prologue GEMM pass, A Z0 is read from a.P0.  p0_supports: false for an instantiation left on the
+// compute form (DESIGN: none).  launch_p0_producer writes P0 [MP][ldp] = Ap Z0 with the fused
+// kernel's MFMA sequence (bit-identical to the product its prologue pass forms), one wave per 16
+// columns, grid = tiles.
+bool p0_supports(int shape, int variant);
+hipError_t launch_fused_shape_p0(int shape, int variant, const FusedArgs& a, int grid,
+                                 hipStream_t s);
+hipError_t launch_fused_shape_p0_savep(int shape, int variant, const FusedArgs& a, int grid,
+                                       hipStream_t s);
+hipError_t launch_p0_producer(int shape, const float* Ap, const float* Z0, int64_t ldz0, int n,
+                              int64_t B, float* P0, int64_t ldp, int grid, hipStream_t s);
 // small-batch row-split form of the fused kernel (path 5, dladmm_fused_rs.hip): 16 columns per
 // workgroup, grid = ceil(B / 16)
 bool rs_supports(int shape, int variant);

@@ -34,7 +34,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .ops import ForwardResult, dladmm_backward, dladmm_forward, dladmm_lena, dladmm_scale_
+from .ops import (ForwardResult, PrologueCache, dladmm_backward, dladmm_forward, dladmm_lena,
+                  dladmm_scale_)
 
 
 def _dev(t: torch.Tensor) -> torch.Tensor:
@@ -213,6 +214,29 @@ class _DLADMMBase(nn.Module):
     # (fp32) backward differentiates that forward; "bf16" is inference-only.
     precision = "f32"
 
+    # Reuse of the prologue product A Z0 and of the packed A across calls (ops.PrologueCache): A
+    # and Z0 are plain tensors, not parameters, and the reference never changes them after
+    # construction.  True: run(), forward and the training ops take both from the model's cache
+    # when its key matches (bit-identical results; ForwardResult.p0_reused tells).  False: every
+    # call computes everything.  In-place ops on A / Z0, assigning new ones, shard_batch_ or another
+    # batch or precision make the key miss by themselves; an edit through `.data` does not bump the
+    # version counter and needs invalidate_cache().
+    reuse_prologue = True
+
+    def _p0_cache(self):
+        if not self.reuse_prologue:
+            return None
+        c = self.__dict__.get("_p0c")
+        if c is None:
+            c = self.__dict__["_p0c"] = PrologueCache()
+        return c
+
+    def invalidate_cache(self):
+        """Drop the cached prologue product and packed A (after editing A or Z0 through .data)."""
+        c = self.__dict__.get("_p0c")
+        if c is not None:
+            c.invalidate()
+
     def run(self, x: torch.Tensor, keep_all: bool = True, loss_kind: int = 0,
             kernel_events=None, want_col_loss: bool = False):
         """Fused forward returning the raw ops.ForwardResult (stacked [K, rows, B] outputs).
@@ -223,7 +247,7 @@ class _DLADMMBase(nn.Module):
                 self.VARIANT, x, self.A, [w.detach() for w in self._weights()],
                 self.Z0, self.E0, self.L0, keep_all=keep_all, want_T=self.RETURNS_T,
                 loss_kind=loss_kind, kernel_events=kernel_events, want_col_loss=want_col_loss,
-                precision=self.precision, **self._tables(dev))
+                precision=self.precision, p0_cache=self._p0_cache(), **self._tables(dev))
 
     def _forward_layers(self, x, nl: int):
         """Run the first `nl` layers; lists Z, E, L (nl entries) and T (nl + 1), differentiable
@@ -242,7 +266,7 @@ class _DLADMMBase(nn.Module):
             tables = _slice_tables(self._tables(self.A.device), nl)
             r = dladmm_forward(self.VARIANT, x, self.A, [w.detach() for w in self._weights()[:nl]],
                                self.Z0, self.E0, self.L0, keep_all=True, want_T=self.RETURNS_T,
-                               precision=self.precision, **tables)
+                               precision=self.precision, p0_cache=self._p0_cache(), **tables)
         T = [r.T[j] for j in range(nl + 1)] if r.T is not None else None
         return ([r.Z[k] for k in range(nl)], [r.E[k] for k in range(nl)],
                 [r.L[k] for k in range(nl)], T)
@@ -356,6 +380,7 @@ class _DLADMMBase(nn.Module):
         Z0, E0, L0 = self._init_state(cols)
         W = [w.detach() for w in self._weights()]
         kw.setdefault("precision", self.precision)
+        kw.setdefault("p0_cache", self._p0_cache())
         return dladmm_forward(self.VARIANT, x, self.A, W, Z0, E0, L0, keep_all=True,
                               **kw, **self._tables(dev, cols))
 
@@ -463,7 +488,8 @@ class _DLADMMFunction(torch.autograd.Function):
         tables = _slice_tables(mod._tables(dev), nl)
         W = [w.detach() for w in mod._weights()[:nl]]
         r = dladmm_forward(mod.VARIANT, x, mod.A, W, mod.Z0, mod.E0, mod.L0, keep_all=True,
-                           want_T=True, want_P=True, precision=_train_precision(mod), **tables)
+                           want_T=True, want_P=True, precision=_train_precision(mod),
+                           p0_cache=mod._p0_cache(), **tables)
         ctx.mod = mod
         ctx.nl = nl
         ctx.tables = tables
@@ -528,7 +554,8 @@ class _DLADMMLossFunction(torch.autograd.Function):
         Z0, E0, L0 = mod._init_state(cols)
         lk = {"l1l1": _lib.LOSS_L1L1, "lasso": _lib.LOSS_LASSO}[kind]
         r = dladmm_forward(mod.VARIANT, x, mod.A, W, Z0, E0, L0, keep_all=True, want_T=True,
-                           loss_kind=lk, want_P=True, precision=_train_precision(mod), **tables)
+                           loss_kind=lk, want_P=True, precision=_train_precision(mod),
+                           p0_cache=mod._p0_cache(), **tables)
         per_layer = (alpha * r.loss_sums[:, 0] + r.loss_sums[:, 1]) / denom  # fp64 [K]
         c = _coef_tensor(coeffs, dev)
         total = (c * per_layer).sum().to(torch.float32)
@@ -585,7 +612,7 @@ class _DLADMMLenaLossFunction(torch.autograd.Function):
         Z0, E0, L0 = mod._init_state(cols)
         r = dladmm_forward(mod.VARIANT, x, mod.A, W, Z0, E0, L0, keep_all=True, want_T=True,
                            loss_kind=_lib.LOSS_L1L1, want_P=True, precision=_train_precision(mod),
-                           **tables)
+                           p0_cache=mod._p0_cache(), **tables)
         c = _coef_tensor(coeffs, dev)
         c32 = c.to(torch.float32)
         ctx.grad = any(ctx.needs_input_grad[8:])

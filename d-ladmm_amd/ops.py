@@ -31,6 +31,7 @@ class ForwardResult:
                    # tiles, 4 fused split-f16, 5 fused row-split, 6 its four-workgroup
                    # form; 0 = nothing launched)
     flags: int = 0  # the plan options (dladmm_flags) the forward ran with; its backward keeps them
+    p0_reused: bool = False  # the load-P0 form ran: A Z0 and the packed A came from a PrologueCache
 
 
 _PLAN_FLAGS = contextvars.ContextVar("dladmm_plan_flags", default=0)
@@ -60,6 +61,68 @@ def plan_flags(**opts):
         yield flags
     finally:
         _PLAN_FLAGS.reset(tok)
+
+
+def _tensor_sig(t: torch.Tensor):
+    """What a PrologueCache remembers of A / Z0: storage address, version counter, shape, strides.
+    None where the version is not tracked (inference tensors): such a call is not cached."""
+    try:
+        return (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()))
+    except RuntimeError:
+        return None
+
+
+class PrologueCache:
+    """Per-model reuse of the prologue product P0 = A Z0 and of the packed A across forward calls
+    (include/dladmm.h, DLADMM_F_P0_SAVE / DLADMM_F_P0_REUSE).  A and Z0 are plain tensors of the
+    model, never parameters (the reference builds them once, main_syn_l1l1_scalar.py:226-234, and
+    still recomputes A.mm(Z0) in every forward, :92); everything derived from parameters is
+    repacked on every call as before.
+
+    One slot per (device, stream), at most MAX_STREAMS (least recently used out): each owns the
+    workspace tensor that holds the packed A and P0 -- never the shared `_workspace`, which any
+    other call on the stream may overwrite, and never another stream's, because the loss partials
+    live in the workspace too.  A slot is valid for one key: the call's variant, m, n, B, layer
+    count and precision, the workspace size (its layout) and, for both A and the Z0 (or
+    column shard of it) actually passed, data_ptr(), _version, shape and strides.  Any in-place op,
+    assignment of a new tensor, shard_batch_ or other batch makes the key miss, and the call then
+    recomputes and refills (p0_reused False).  The slot keeps A and Z0 alive, so a freed tensor's
+    address cannot come back under the same key.  NOT seen: an edit through `.data` (it does not
+    bump the version counter) -- call invalidate() after one."""
+    MAX_STREAMS = 4
+
+    def __init__(self):
+        from collections import OrderedDict
+        self._slots = OrderedDict()
+
+    def invalidate(self):
+        self._slots.clear()
+
+    def __deepcopy__(self, memo):
+        return PrologueCache()
+
+    def __reduce__(self):
+        return (PrologueCache, ())
+
+    def lookup(self, skey, key, nbytes, dev):
+        """The slot's workspace (allocated or grown on a miss) and whether it holds `key`'s
+        products.  A miss leaves the slot without a key until commit()."""
+        slot = self._slots.pop(skey, None)
+        hit = slot is not None and slot["key"] == key and slot["ws"].numel() >= nbytes
+        if not hit:
+            ws = slot["ws"] if slot is not None and slot["ws"].numel() >= nbytes else \
+                torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+            slot = {"ws": ws, "key": None, "keep": None}
+        self._slots[skey] = slot   # most recently used last
+        while len(self._slots) > self.MAX_STREAMS:
+            self._slots.popitem(last=False)
+        return slot["ws"], hit
+
+    def commit(self, skey, key, keep):
+        """The DLADMM_F_P0_SAVE call was enqueued: the slot now holds `key`'s products."""
+        slot = self._slots.get(skey)
+        if slot is not None:
+            slot["key"], slot["keep"] = key, keep
 
 
 def _f32_dev(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -164,7 +227,8 @@ def dladmm_forward(variant: int, X: torch.Tensor, A: torch.Tensor, W: Sequence[t
                    out: Optional[ForwardResult] = None,
                    kernel_events: Optional[tuple] = None,
                    want_col_loss: bool = False, precision: str = "f32",
-                   want_P: bool = False, flags: Optional[int] = None) -> ForwardResult:
+                   want_P: bool = False, flags: Optional[int] = None,
+                   p0_cache: Optional[PrologueCache] = None) -> ForwardResult:
     """Run the whole K-layer forward of `variant` (dladmm_variant) on X's device.
 
     X: (m, B); A: (m, n); W: K tensors (n, m) (fc[k].weight; V5 passes the shared one K times);
@@ -176,6 +240,9 @@ def dladmm_forward(variant: int, X: torch.Tensor, A: torch.Tensor, W: Sequence[t
     other path result.P stays None and the backward recomputes it.
     flags: plan options (include/dladmm.h dladmm_flags); None = those of the enclosing
     plan_flags block.
+    p0_cache: a PrologueCache (the models pass their own): where the call runs the fused fp32
+    kernel (path 1) outside a graph capture, A Z0 and the packed A are taken from it when its key
+    matches (result.p0_reused) and left in it otherwise.  Bit-identical results either way.
     """
     L = _lib.lib()
     _f32_dev(X, "X")
@@ -214,7 +281,7 @@ def dladmm_forward(variant: int, X: torch.Tensor, A: torch.Tensor, W: Sequence[t
         raise ValueError(f"dladmm: precision must be one of {sorted(_PRECISIONS)}, "
                          f"got {precision!r}")
     d.precision = _PRECISIONS[precision]
-    # (the fused paths 1, 4, 5 and 6 all store P_k; every other path leaves result.P None)
+    # the fused kernels (paths 1, 4, 5 and 6) store P_k; every other path leaves result.P None
     if want_P and keep_all and out.P is None and L.dladmm_fwd_path(ctypes.byref(d)) in (1, 4, 5, 6):
         out.P = torch.empty((K, m, B), device=dev, dtype=torch.float32)
         d.P = out.P.data_ptr()
@@ -233,10 +300,32 @@ def dladmm_forward(variant: int, X: torch.Tensor, A: torch.Tensor, W: Sequence[t
         path = L.dladmm_fwd_path(ctypes.byref(d))
         _lib.check(path if path < 0 else -7)
     out.path = L.dladmm_fwd_path(ctypes.byref(d))
-    ws = _workspace(dev, wsb)
-    d.workspace, d.workspace_bytes = ws.data_ptr(), wsb
     stream = torch.cuda.current_stream(dev).cuda_stream
+    # Reuse of the prologue product: never while the stream is capturing (a replay cannot
+    # re-check a key), only on path 1, and only where the plan reserves the P0 region (the
+    # workspace grows with the flag: fp32 proper).  out.flags keeps the caller's plan options.
+    ws = ckey = None
+    out.p0_reused = False
+    if p0_cache is not None and out.path == 1 and not torch.cuda.is_current_stream_capturing():
+        sa, sz = _tensor_sig(A), _tensor_sig(Z0)
+        d.flags = out.flags | _lib.F_P0_SAVE
+        wsb_p0 = L.dladmm_fwd_workspace_bytes(ctypes.byref(d))
+        if sa is not None and sz is not None and wsb_p0 > wsb:
+            # wsb_p0 pins the workspace layout (layer count, weight sharing): P0 sits at its end
+            ckey = (variant, m, n, B, K, precision, sa, sz, wsb_p0)
+            skey = (dev.type, dev.index, stream)
+            ws, out.p0_reused = p0_cache.lookup(skey, ckey, wsb_p0, dev)
+            wsb = wsb_p0
+            d.flags = (out.flags & ~_lib.F_P0_SAVE) | _lib.F_P0_REUSE if out.p0_reused \
+                else out.flags | _lib.F_P0_SAVE
+        else:
+            d.flags = out.flags
+    if ws is None:
+        ws = _workspace(dev, wsb)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), wsb
     _lib.check(L.dladmm_fwd_f32(ctypes.byref(d), ctypes.c_void_p(stream)))
+    if ckey is not None and not out.p0_reused:
+        p0_cache.commit(skey, ckey, (A, Z0))
     del keep
     return out
 

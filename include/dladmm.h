@@ -185,10 +185,29 @@ enum dladmm_flags {
                                   A/B)                                                             */
   DLADMM_F_NO_XSPLIT = 128,    /* forward: the one-workgroup row split (path 5) where the
                                   four-workgroup one (path 6) would run                            */
-  DLADMM_F_ROWSPLIT_ROWP = 256 /* forward: the row-split forms (paths 5 / 6) also for the
+  DLADMM_F_ROWSPLIT_ROWP = 256,/* forward: the row-split forms (paths 5 / 6) also for the
                                   per-row-parameter variants V2 / V3, which keep path 1 without
                                   it; the backward follows the forward as for the other variants
                                   (dladmm_bwd_path 2 / 3).  No effect on any other variant         */
+  /* Reuse of the prologue product P0 = A Z0 across calls.  A and Z0 are plain tensors in the
+     reference (never trained), yet every forward recomputes A.mm(Z0)
+     (main_syn_l1l1_scalar.py:92); a caller that keeps them from call to call saves that GEMM
+     pass and the repacking of A.  Both flags act only on path 1 with DLADMM_PREC_F32; everywhere
+     else they are ignored and everything is computed (always correct).  dladmm_fwd_path() does
+     not depend on them; dladmm_fwd_workspace_bytes() grows by the P0 region where they act.
+     The results are bit-identical with and without them.  The backward ignores both. */
+  DLADMM_F_P0_SAVE = 512,      /* the call runs as without the flag and also leaves the packed A
+                                  and P0 in the workspace for later DLADMM_F_P0_REUSE calls.  Wins
+                                  over DLADMM_F_P0_REUSE when both are set                         */
+  DLADMM_F_P0_REUSE = 1024     /* the call packs no A and forms no A Z0: it reads both from the
+                                  workspace.  The caller's contract: `workspace` is the one a
+                                  DLADMM_F_P0_SAVE call ran on (in stream order before this call)
+                                  with the same variant, m, n, batch, precision, layer count and
+                                  weight sharing (P0 sits at the end of the workspace: the same
+                                  dladmm_fwd_workspace_bytes()) and the same A and Z0 contents and
+                                  strides, and nothing but dladmm_fwd_f32 calls under that same
+                                  contract has written it since.  The weights, the parameters,
+                                  every other input and the outputs may differ                    */
 };
 
 /* ABI version the library was built with. */
