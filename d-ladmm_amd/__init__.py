@@ -10,11 +10,14 @@ from .model import (DLADMMNet, DLADMMNetFull, DLADMMNetLasso, DLADMMNetLTheta,  
                     DLADMMNetScalarZ0, VARIANTS, load_checkpoint)
 from .model import DLADMMNetNewS, DLADMMNetPTiedNewS, DLADMMNetTiedNewS  # noqa: F401
 from .lskm import DLADMMNetLSKM  # noqa: F401
+from .lskm_news import (DLADMMNetNewSLSKM, DLADMMNetPTiedNewSLSKM,  # noqa: F401
+                        DLADMMNetTiedNewSLSKM)
 from .ops import (BackwardResult, ForwardResult, dladmm_backward, dladmm_forward,  # noqa: F401
                   plan_flags)
 
 __all__ = ["DLADMMNet", "DLADMMNetLTheta", "DLADMMNetFull", "DLADMMNetScalar",
            "DLADMMNetScalarSl2", "DLADMMNetScalarZ0",
            "DLADMMNetScalarTied", "DLADMMNetLasso", "DLADMMNetNewS", "DLADMMNetTiedNewS",
-           "DLADMMNetPTiedNewS", "DLADMMNetLSKM", "VARIANTS", "load_checkpoint",
+           "DLADMMNetPTiedNewS", "DLADMMNetLSKM", "DLADMMNetNewSLSKM",
+           "DLADMMNetTiedNewSLSKM", "DLADMMNetPTiedNewSLSKM", "VARIANTS", "load_checkpoint",
            "dladmm_forward", "dladmm_backward", "ForwardResult", "BackwardResult"]

@@ -25,8 +25,11 @@ F_NO_XSPLIT = 128
 F_ROWSPLIT_ROWP = 256
 F_P0_SAVE = 512      # path 1, fp32: also leave the packed A and P0 = A Z0 in the workspace
 F_P0_REUSE = 1024    # path 1, fp32: read them from the workspace a F_P0_SAVE call ran on
+F_ELZ = 2048         # `layers` steps E, L, Z from (Z0, E0, L0): the newS loop's entry (paths 1, 5)
+F_ELZ_TAIL = 4096    # with F_ELZ and P: also P[layers] = A Z[layers - 1]
 # enum dladmm_variant
 V1_LENA, V2_LTHETA, V3_FULL, V4_SCALAR, V5_TIED, V6_LASSO = 1, 2, 3, 4, 5, 6
+V7_SCALAR_V1E = 7    # the V1 E-step with scalar parameters and a step (the newS KM iteration)
 # enum dladmm_loss_kind
 LOSS_NONE, LOSS_L1L1, LOSS_LASSO = 0, 1, 2
 # enum dladmm_param_slot
@@ -35,7 +38,7 @@ P_BETA1, P_BETA2, P_BETA3, P_SS2, P_SS2B, P_THETA_E, P_THETA_Z, P_S1 = range(8)
 # every symbol include/dladmm.h declares (checked by tests/test_capi.py)
 EXPORTED = ("dladmm_abi_version", "dladmm_fwd_workspace_bytes", "dladmm_fwd_path",
             "dladmm_fwd_f32", "dladmm_bwd_workspace_bytes", "dladmm_bwd_path", "dladmm_bwd_f32",
-            "dladmm_safeguard_f32", "dladmm_colobj_f32", "dladmm_lena_workspace_bytes",
+            "dladmm_safeguard_f32", "dladmm_safeguard_news_f32", "dladmm_colobj_f32", "dladmm_lena_workspace_bytes",
             "dladmm_lena_f32", "dladmm_scale_f32", "dladmm_error_string")
 # enum dladmm_mu_updater
 MU_NONE, MU_EMA, MU_GS, MU_RT = 0, 1, 2, 3
@@ -100,6 +103,20 @@ class SafeguardDesc(ctypes.Structure):
     ]
 
 
+class SafeguardNewsDesc(ctypes.Structure):
+    """Mirror of `struct dladmm_safeguard_news_desc` (include/dladmm.h)."""
+    _fields_ = [
+        ("abi_version", _i32), ("m", _i32), ("n", _i32), ("batch", _i32), ("ld", _i64),
+        ("X", _fp),
+        ("Zl", _fp), ("El", _fp), ("Ll", _fp),
+        ("Zk", _fp), ("Ek", _fp), ("Lk", _fp),
+        ("En", _fp), ("Znn", _fp), ("Pn", _fp), ("Pnn", _fp),
+        ("Zo", _fp), ("Eo", _fp), ("Lo", _fp),
+        ("mu", _fp), ("norm_out", _fp), ("count", _fp), ("mask", _fp), ("inv_bs", _fp),
+        ("delta", ctypes.c_double), ("updater", _i32), ("mu_param", ctypes.c_float),
+    ]
+
+
 class ColObjDesc(ctypes.Structure):
     """Mirror of `struct dladmm_colobj_desc` (include/dladmm.h)."""
     _fields_ = [
@@ -159,6 +176,8 @@ def lib():
     L.dladmm_bwd_f32.argtypes = [ctypes.POINTER(BwdDesc), ctypes.c_void_p]
     L.dladmm_safeguard_f32.restype = ctypes.c_int
     L.dladmm_safeguard_f32.argtypes = [ctypes.POINTER(SafeguardDesc), ctypes.c_void_p]
+    L.dladmm_safeguard_news_f32.restype = ctypes.c_int
+    L.dladmm_safeguard_news_f32.argtypes = [ctypes.POINTER(SafeguardNewsDesc), ctypes.c_void_p]
     L.dladmm_colobj_f32.restype = ctypes.c_int
     L.dladmm_colobj_f32.argtypes = [ctypes.POINTER(ColObjDesc), ctypes.c_void_p]
     L.dladmm_lena_workspace_bytes.restype = ctypes.c_size_t

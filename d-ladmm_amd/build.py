@@ -17,6 +17,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 UNITS = ("dladmm_capi.hip", "dladmm_fused.hip", "dladmm_fused_savep.hip",
+         # the fused kernel with the ELZ entry / exit modes (V4 / V5 / V7)
+         "dladmm_fused_elz.hip",
          # the fused kernel's load-P0 form (inference / training) and the P0 producer
          "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip", "dladmm_fused_x3.hip",
          "dladmm_fused_x3_savep.hip", "dladmm_fused_rs.hip", "dladmm_fused_xs.hip",

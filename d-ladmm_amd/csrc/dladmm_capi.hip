@@ -342,10 +342,12 @@ struct Plan {
   int64_t ldzw;               // path 4: lean-mode Z_k workspace row stride
 };
 
+inline bool fits_32bit(const dladmm_fwd_desc* d);
+
 inline int validate(const dladmm_fwd_desc* d) {
   if (!d) return DLADMM_E_NULL;
   if (d->abi_version != DLADMM_ABI_VERSION) return DLADMM_E_ABI_VERSION;
-  if (d->variant < DLADMM_V1_LENA || d->variant > DLADMM_V6_LASSO) return DLADMM_E_VARIANT;
+  if (d->variant < DLADMM_V1_LENA || d->variant > DLADMM_V7_SCALAR_V1E) return DLADMM_E_VARIANT;
   if (d->m < 1 || d->n < 1 || d->batch < 1) return DLADMM_E_SHAPE;
   if (d->layers < 1 || d->layers > DLADMM_MAX_LAYERS) return DLADMM_E_LAYERS;
   if (d->loss_kind < 0 || d->loss_kind > 2) return DLADMM_E_UNSUPPORTED;
@@ -375,6 +377,22 @@ inline int validate(const dladmm_fwd_desc* d) {
   if (d->ld_x < B || d->ld_z0 < B || d->ld_e0 < B || d->ld_l0 < B || d->ld_out < B)
     return DLADMM_E_SHAPE;
   if (d->ld_a < d->n || d->ld_w < d->m) return DLADMM_E_SHAPE;
+  // V7 (the scalar V1 form) and the DLADMM_F_ELZ steps exist on the fused fp32 kernels only
+  // (paths 1, 5, 6): no per-layer, split-f16 or bf16 plan, and V7 keeps P for nothing but the
+  // ELZ steps' safeguard norm
+  const bool elz = (d->flags & DLADMM_F_ELZ) != 0;
+  if (v == DLADMM_V7_SCALAR_V1E || elz) {
+    if (d->precision != DLADMM_PREC_F32 || (d->flags & DLADMM_F_PER_LAYER) ||
+        pick_shape(d->m, d->n) < 0 || !fits_32bit(d))
+      return DLADMM_E_UNSUPPORTED;
+    if (v == DLADMM_V7_SCALAR_V1E && d->P && !elz) return DLADMM_E_UNSUPPORTED;
+  }
+  if (elz) {
+    if (v != DLADMM_V4_SCALAR && v != DLADMM_V5_TIED && v != DLADMM_V7_SCALAR_V1E)
+      return DLADMM_E_UNSUPPORTED;
+    if (!d->keep_all || d->loss_kind) return DLADMM_E_UNSUPPORTED;
+  }
+  if ((d->flags & DLADMM_F_ELZ_TAIL) && (!elz || !d->P)) return DLADMM_E_UNSUPPORTED;
   return 0;
 }
 
@@ -443,7 +461,8 @@ inline bool use_rowsplit(const dladmm_fwd_desc* d, int shape) {
 // memory once per product), where the whole grid fits one workgroup per CU (B <= 1,024 on 256
 // CUs): a quarter of path 5's MFMA cycles per SIMD.  DLADMM_F_NO_XSPLIT keeps path 5.
 inline bool use_xsplit(const dladmm_fwd_desc* d, int shape) {
-  return use_rowsplit(d, shape) && !(d->flags & DLADMM_F_NO_XSPLIT) &&
+  // the DLADMM_F_ELZ steps run on paths 1 and 5
+  return use_rowsplit(d, shape) && !(d->flags & (DLADMM_F_NO_XSPLIT | DLADMM_F_ELZ)) &&
          xs_grid(d->batch) <= device_cus();
 }
 
@@ -501,6 +520,7 @@ inline int make_plan(const dladmm_fwd_desc* d, Plan* p) {
     // the region goes after every existing one, so their offsets stay (the load form addresses it
     // with 32-bit buffer offsets)
     if (p->path == 1 && (d->flags & (DLADMM_F_P0_SAVE | DLADMM_F_P0_REUSE)) &&
+        !(d->flags & DLADMM_F_ELZ) &&
         d->precision == DLADMM_PREC_F32 && p0_supports(s, d->variant) &&
         (int64_t)p->MP * p->ldl * 4 < ((int64_t)1 << 31)) {
       p->p0 = true;
@@ -608,6 +628,7 @@ inline int run_fused(const dladmm_fwd_desc* d, const Plan& p, char* ws, hipStrea
   FusedArgs a{};
   a.m = d->m; a.n = d->n; a.B = d->batch; a.K = d->layers;
   a.keep_all = d->keep_all ? 1 : 0; a.loss_kind = d->loss_kind; a.ldl = p.ldl;
+  a.elz = (d->flags & DLADMM_F_ELZ) ? ((d->flags & DLADMM_F_ELZ_TAIL) ? 2 : 1) : 0;
   a.X = d->X; a.ldx = d->ld_x;
   a.Z0 = d->Z0; a.ldz0 = d->ld_z0;
   a.E0 = d->E0; a.lde0 = d->ld_e0;
@@ -657,6 +678,7 @@ inline int run_fused(const dladmm_fwd_desc* d, const Plan& p, char* ws, hipStrea
   hipError_t e = p.path == 6 ? launch_fused_xs(p.shape, d->variant, a, s)
                  : p.path == 5
                     ? launch_fused_rs(p.shape, d->variant, a, ceil_div(d->batch, 16), s)
+                 : a.elz ? launch_fused_shape_elz(p.shape, d->variant, a, p.tiles, s)
                  : p0_reuse
                     ? (savep ? launch_fused_shape_p0_savep : launch_fused_shape_p0)(
                           p.shape, d->variant, a, p.tiles, s)
@@ -891,6 +913,9 @@ inline int validate_bwd(const dladmm_bwd_desc* d) {
   if (int e = validate(&d->fwd)) return e;
   const dladmm_fwd_desc& f = d->fwd;
   if (!f.keep_all || !f.T) return DLADMM_E_UNSUPPORTED;
+  // inference only: the scalar V1 form and the ELZ steps have no backward
+  if (f.variant == DLADMM_V7_SCALAR_V1E || (f.flags & (DLADMM_F_ELZ | DLADMM_F_ELZ_TAIL)))
+    return DLADMM_E_UNSUPPORTED;
   // backward kernels are fp32; F32_SPLIT moves only the weight-gradient GEMM (make_bwd_plan)
   if (f.precision != DLADMM_PREC_F32 && f.precision != DLADMM_PREC_F32_SPLIT)
     return DLADMM_E_UNSUPPORTED;

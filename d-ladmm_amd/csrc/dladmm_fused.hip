@@ -13,6 +13,7 @@ hipError_t dispatch_variant(int variant, const FusedArgs& a, int grid, hipStream
     case DLADMM_V4_SCALAR: return launch_fused<MP, NP, EM_VVAR, PK_SCALAR, false>(a, grid, s);
     case DLADMM_V5_TIED: return launch_fused<MP, NP, EM_VVAR, PK_S1, false>(a, grid, s);
     case DLADMM_V6_LASSO: return launch_fused<MP, NP, EM_LASSO, PK_SCALAR, false>(a, grid, s);
+    case DLADMM_V7_SCALAR_V1E: return launch_fused<MP, NP, EM_V1, PK_S1, false>(a, grid, s);
   }
   return hipErrorInvalidValue;
 }

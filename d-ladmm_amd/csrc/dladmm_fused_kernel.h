@@ -174,8 +174,13 @@ struct WinCount {
 // prologue GEMM pass is not run: the ring stream starts at W_0, the prologue's epilogue rows run
 // up front from the loaded product, and the last pair's product goes to qa / qb so that G1(0)
 // runs its rows as in the compute form.  Everything from G1(0) on is the compute form's code.
-template <int MP, int NP, int EMODE, int PKIND, bool SAVEP, bool P0LOAD = false>
+// ELZ: the DLADMM_F_ELZ entry / exit modes (a.elz = 1, or 2 with the tail).  A compile-time
+// parameter like P0LOAD: the register-resident kernel has no room for a run-time mode, and every
+// instantiation without it stays instruction for instruction what it was (a.elz is not read).
+// Instantiated for V4 / V5 / V7 only (dladmm_fused_elz.hip).
+template <int MP, int NP, int EMODE, int PKIND, bool SAVEP, bool P0LOAD = false, bool ELZ = false>
 __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
+  static_assert(!(P0LOAD && ELZ), "the ELZ entry computes its own prologue product");
   using F = Fused<MP, NP, EMODE, PKIND>;
   constexpr int MB = F::MB, NB = F::NB, CF = F::CF, NCH = F::NCH, TAB = F::TAB;
   using Win = WinCount<MB, NB, CF, PKIND, SAVEP>;
@@ -193,6 +198,7 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   const int m = a.m, n = a.n, K = a.K;
   const bool lossz = a.loss_kind != 0;
   const bool lasso = __builtin_amdgcn_readfirstlane(a.loss_kind) == DLADMM_LOSS_LASSO;
+  const int elz = ELZ ? __builtin_amdgcn_readfirstlane(a.elz) : 0;
 
   // per-lane byte offset of (row 4g, column col) in a [rows][ld] fp32 matrix; kOOB for padding
   auto lane_off = [&](int64_t ld) -> uint32_t {
@@ -282,11 +288,14 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
       const int kk = k < 0 ? 0 : k;
       const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
       cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
-      p.b2 = sp[DLADMM_P_BETA2];
-      p.b3 = sp[DLADMM_P_BETA3];
-      p.ss2 = sp[DLADMM_P_SS2];
-      p.ss2b = sp[DLADMM_P_SS2B];
-      p.the = shrink_params(sp[DLADMM_P_THETA_E]);
+      // DLADMM_F_ELZ: pass G2(k) is the E / L half of step k + 1, on that row's slots
+      cfloat_p se = (cfloat_p)a.scal + (elz ? kn : kk) * DLADMM_NSCALAR;
+      p.b2 = se[DLADMM_P_BETA2];
+      // the scalar V1 form (V7) has no beta3: L = L + beta1 T, as everywhere in EM_V1
+      p.b3 = (EMODE == EM_V1 && PKIND == PK_S1) ? se[DLADMM_P_BETA1] : se[DLADMM_P_BETA3];
+      p.ss2 = se[DLADMM_P_SS2];
+      p.ss2b = se[DLADMM_P_SS2B];
+      p.the = shrink_params(se[DLADMM_P_THETA_E]);
       p.thz = shrink_params(sp[DLADMM_P_THETA_Z]);
       if constexpr (PKIND == PK_S1) p.s1 = sp[DLADMM_P_S1];
       p.b1n = ((cfloat_p)a.scal)[kn * DLADMM_NSCALAR + DLADMM_P_BETA1];
@@ -643,7 +652,8 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
           constexpr int h = i / 4, r = i % 4;
           if constexpr (rows_at(jb, MB, i)) {
             if constexpr (p == 0) {
-              epi2_row(Pp, Op, k - 1, k == 0, MB - 2 + h, h, r, h ? qb : qa, h ? xb : xa);
+              epi2_row(Pp, Op, k - 1, k == 0 && !elz, MB - 2 + h, h, r, h ? qb : qa,
+                       h ? xb : xa);
               if constexpr (i == 7) flush_loss(k - 1);
             } else {
               epi1_row(P, rzo, k, 2 * p - 2 + h, r, h ? qb : qa);
@@ -699,7 +709,7 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
             if constexpr (p == 0) {
               if constexpr (!PRO) epi1_row(P, rzo, k, NB - 2 + h, r, h ? qb : qa);
             } else {
-              epi2_row(P, O, k, PRO, 2 * p - 2 + h, h, r, h ? qb : qa, h ? xb : xa);
+              epi2_row(P, O, k, PRO && !elz, 2 * p - 2 + h, h, r, h ? qb : qa, h ? xb : xa);
               prefetch_part(k, PRO, I_);  // this row's beta slot, for pair p
             }
           }
@@ -738,10 +748,13 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
 
   // ---------------------------------------------------------------- prologue + K layers
   // G2(-1) [A Z0 - X -> T0, Var_0], then per layer G1(k) [Z_k], G2(k) [E_k, L_k, T_k+1, Var_k+1]
+  // DLADMM_F_ELZ (the ELZ instantiations: a.elz, keep_all): the prologue pass is the E / L half of
+  // step 0 (its rows run the full epilogue and store E / L / T / P [0]); G2(k) writes slab k + 1
   const rsrc_t none = mkrsrc(nullptr, 0u);
   LayerP Pp = layer_params(-1);
-  OutR Op{none, none,
-          mkrsrc(a.keep_all ? a.To : nullptr, (a.keep_all && a.To) ? mbytes : 0u), none};
+  OutR Op{elz ? mkrsrc(a.Eo, mbytes) : none, elz ? mkrsrc(a.Lo, mbytes) : none,
+          mkrsrc(a.keep_all ? a.To : nullptr, (a.keep_all && a.To) ? mbytes : 0u),
+          (SAVEP && elz) ? mkrsrc(a.Po, a.Po ? mbytes : 0u) : none};
   if constexpr (P0LOAD) {
     // after the priming barrier: layer 0's row table (PK_ROW) has landed for every wave
     {
@@ -809,11 +822,21 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     st_g1 += tb - ta;
 #endif
-    const OutR O{mkrsrc(a.Eo + (int64_t)ko * m * a.ldo, st ? mbytes : 0u),
-                 mkrsrc(a.Lo + (int64_t)ko * m * a.ldo, st ? mbytes : 0u),
+    // DLADMM_F_ELZ: the run ends with Z_{K-1} -- the rows of G1(K-1)'s last pair, which G2 would
+    // run -- or (tail) with a product pass that stores only P[K]
+    const bool zlast = elz && k == K - 1;
+    if (zlast && elz == 1) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) epi1_row(P, rzo, k, NB - 2 + i / 4, i % 4, i < 4 ? qa : qb);
+      break;
+    }
+    const int ke = elz ? k + 1 : ko, kp = elz ? k + 1 : k;
+    const bool sel = st && !zlast;
+    const OutR O{mkrsrc(a.Eo + (int64_t)ke * m * a.ldo, sel ? mbytes : 0u),
+                 mkrsrc(a.Lo + (int64_t)ke * m * a.ldo, sel ? mbytes : 0u),
                  mkrsrc(a.To ? a.To + (int64_t)(a.keep_all ? k + 1 : 0) * m * a.ldo : nullptr,
-                        (a.To && st) ? mbytes : 0u),
-                 mkrsrc(SAVEP && a.Po && a.keep_all ? a.Po + (int64_t)k * m * a.ldo : nullptr,
+                        (a.To && sel) ? mbytes : 0u),
+                 mkrsrc(SAVEP && a.Po && a.keep_all ? a.Po + (int64_t)kp * m * a.ldo : nullptr,
                         SAVEP && a.Po && a.keep_all ? mbytes : 0u)};
     g2_pass(std::false_type{}, k, P, O, rzo);
 #if DLADMM_STAMP
@@ -824,13 +847,15 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
     Pp = P;
     Op = O;
   }
-  // epilogue of the last G2 pair of layer K-1
-  load_x(MB / 2 - 1);
+  // epilogue of the last G2 pair of layer K-1 (DLADMM_F_ELZ without the tail ended above)
+  if (elz != 1) {
+    load_x(MB / 2 - 1);
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
-    epi2_row(Pp, Op, K - 1, false, MB - 2 + i / 4, i / 4, i % 4, i < 4 ? qa : qb,
-             i < 4 ? xa : xb);
-  flush_loss(K - 1);
+    for (int i = 0; i < 8; ++i)
+      epi2_row(Pp, Op, K - 1, false, MB - 2 + i / 4, i / 4, i % 4, i < 4 ? qa : qb,
+               i < 4 ? xa : xb);
+    flush_loss(K - 1);
+  }
   // drain: the ring's last LDS-DMA must land before the workgroup's LDS is released
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if DLADMM_STAMP
@@ -847,10 +872,10 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
 }
 
 
-template <int MP, int NP, int EM, int PK, bool SAVEP, bool P0LOAD = false>
+template <int MP, int NP, int EM, int PK, bool SAVEP, bool P0LOAD = false, bool ELZ = false>
 hipError_t launch_fused(const FusedArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((fused_kernel<MP, NP, EM, PK, SAVEP, P0LOAD>), dim3(grid), dim3(256), 0, s,
-                     a);
+  hipLaunchKernelGGL((fused_kernel<MP, NP, EM, PK, SAVEP, P0LOAD, ELZ>), dim3(grid), dim3(256), 0,
+                     s, a);
   return hipGetLastError();
 }
 

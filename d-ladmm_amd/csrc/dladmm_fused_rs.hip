@@ -34,7 +34,10 @@
 
 namespace dladmm {
 
-template <int MP, int NP, int EMODE, int PKIND>
+// ELZ: the DLADMM_F_ELZ entry / exit modes (a.elz = 1, or 2 with the tail), a compile-time
+// parameter as in the fused kernel: instantiated for V4 / V5 / V7, and every instantiation
+// without it is instruction for instruction what it was.
+template <int MP, int NP, int EMODE, int PKIND, bool ELZ = false>
 __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   constexpr int MB = MP / 16, NB = NP / 16;
   constexpr int NB4 = NB / kWaves, MB4 = MB / kWaves;  // output blocks per wave
@@ -57,6 +60,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   auto lane_off = [&](int64_t ld) -> uint32_t {
     return cv ? (uint32_t)((col + (int64_t)(4 * g) * ld) * 4) : kOOB;
   };
+  const int elz = ELZ ? __builtin_amdgcn_readfirstlane(a.elz) : 0;
   const int b1o = w * NB4, b2o = w * MB4;  // first output block of this wave in G1 / G2
 
   float Zr[NB4][4], Er[MB4][4], Lr[MB4][4], Xr[MB4][4];
@@ -96,11 +100,14 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
     const int kk = k < 0 ? 0 : k;
     const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
     cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
-    p.b2 = sp[DLADMM_P_BETA2];
-    p.b3 = sp[DLADMM_P_BETA3];
-    p.ss2 = sp[DLADMM_P_SS2];
-    p.ss2b = sp[DLADMM_P_SS2B];
-    p.the = shrink_params(sp[DLADMM_P_THETA_E]);
+    // DLADMM_F_ELZ: pass G2(k) is the E / L half of step k + 1, on that row's slots
+    cfloat_p se = (cfloat_p)a.scal + (elz ? kn : kk) * DLADMM_NSCALAR;
+    p.b2 = se[DLADMM_P_BETA2];
+    // the scalar V1 form (V7) has no beta3: L = L + beta1 T, as everywhere in EM_V1
+    p.b3 = (EMODE == EM_V1 && PKIND == PK_S1) ? se[DLADMM_P_BETA1] : se[DLADMM_P_BETA3];
+    p.ss2 = se[DLADMM_P_SS2];
+    p.ss2b = se[DLADMM_P_SS2B];
+    p.the = shrink_params(se[DLADMM_P_THETA_E]);
     p.thz = shrink_params(sp[DLADMM_P_THETA_Z]);
     if constexpr (PKIND == PK_S1) p.s1 = sp[DLADMM_P_S1];
     p.b1n = ((cfloat_p)a.scal)[kn * DLADMM_NSCALAR + DLADMM_P_BETA1];
@@ -256,7 +263,8 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   struct OutR { rsrc_t e, l, t, p; };
   const rsrc_t ra = mkrsrc(a.Ap + (int64_t)(b2o / 2) * NB * 2 * kFrag, (uint32_t)(S2 * 2 * kFrag * 4));
   auto g2_pass = [&](auto PRO_, int k, const LayerP& P, const OutR& O) {
-    constexpr bool PRO = decltype(PRO_)::value;
+    // DLADMM_F_ELZ: the prologue pass runs the full epilogue (E / L half of step 0)
+    const bool PRO = decltype(PRO_)::value && !elz;
     load_betas(k);
     f32x4 fa[RS_PF], fb[RS_PF];
     static_for<RS_PF>([&](auto I_) {
@@ -362,8 +370,9 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   const rsrc_t none = mkrsrc(nullptr, 0u);
   __syncthreads();  // every wave's Z0 blocks are in zx
   {
-    const OutR Op{none, none,
-                  mkrsrc(a.keep_all ? a.To : nullptr, (a.keep_all && a.To) ? mbytes : 0u), none};
+    const rsrc_t t0 = mkrsrc(a.keep_all ? a.To : nullptr, (a.keep_all && a.To) ? mbytes : 0u);
+    const OutR Op{elz ? mkrsrc(a.Eo, mbytes) : none, elz ? mkrsrc(a.Lo, mbytes) : none, t0,
+                  elz ? mkrsrc(a.Po, a.Po ? mbytes : 0u) : none};
     g2_pass(std::true_type{}, -1, layer_params(-1), Op);
   }
   regsum = fit1 = fit2 = 0.f;  // the prologue's sums are not an objective
@@ -374,11 +383,17 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
     const LayerP P = layer_params(k);
     g1_pass(k, P, mkrsrc(a.Zo + (int64_t)ko * n * a.ldo, st ? zbytes : 0u));
     __syncthreads();  // Z_k complete; every wave is done reading Var_k
-    const OutR O{mkrsrc(a.Eo + (int64_t)ko * m * a.ldo, st ? mbytes : 0u),
-                 mkrsrc(a.Lo + (int64_t)ko * m * a.ldo, st ? mbytes : 0u),
+    // DLADMM_F_ELZ (keep_all): the run ends with Z_{K-1}, or (tail) with a product pass that
+    // stores only P[K]; the passes before it write slab k + 1 of E / L / P
+    const bool zlast = elz && k == K - 1;
+    if (zlast && elz == 1) break;
+    const int ke = elz ? k + 1 : ko, kp = elz ? k + 1 : k;
+    const bool sel = st && !zlast;
+    const OutR O{mkrsrc(a.Eo + (int64_t)ke * m * a.ldo, sel ? mbytes : 0u),
+                 mkrsrc(a.Lo + (int64_t)ke * m * a.ldo, sel ? mbytes : 0u),
                  mkrsrc(a.To ? a.To + (int64_t)(a.keep_all ? k + 1 : 0) * m * a.ldo : nullptr,
-                        (a.To && st) ? mbytes : 0u),
-                 mkrsrc(a.Po && a.keep_all ? a.Po + (int64_t)k * m * a.ldo : nullptr,
+                        (a.To && sel) ? mbytes : 0u),
+                 mkrsrc(a.Po && a.keep_all ? a.Po + (int64_t)kp * m * a.ldo : nullptr,
                         a.Po && a.keep_all ? mbytes : 0u)};
     g2_pass(std::false_type{}, k, P, O);
     if (lossz) stage_loss();
@@ -387,21 +402,29 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   }
 }
 
-template <int MP, int NP, int EM, int PK>
+template <int MP, int NP, int EM, int PK, bool ELZ = false>
 hipError_t launch_rs(const FusedArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((fused_rs_kernel<MP, NP, EM, PK>), dim3(grid), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((fused_rs_kernel<MP, NP, EM, PK, ELZ>), dim3(grid), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 // every variant at the 256 x 512 shape (the plan admits V2 / V3 only under
 // DLADMM_F_ROWSPLIT_ROWP: dladmm_capi.hip use_rowsplit)
 bool rs_supports(int shape, int variant) {
-  return shape == 2 && variant >= DLADMM_V1_LENA && variant <= DLADMM_V6_LASSO;
+  return shape == 2 && variant >= DLADMM_V1_LENA && variant <= DLADMM_V7_SCALAR_V1E;
 }
 
 hipError_t launch_fused_rs(int shape, int variant, const FusedArgs& a, int grid, hipStream_t s) {
   if (shape != 2) return hipErrorInvalidValue;
   constexpr int MP = kShapeMP[2], NP = kShapeNP[2];
+  if (a.elz) {
+    switch (variant) {
+      case DLADMM_V4_SCALAR: return launch_rs<MP, NP, EM_VVAR, PK_SCALAR, true>(a, grid, s);
+      case DLADMM_V5_TIED: return launch_rs<MP, NP, EM_VVAR, PK_S1, true>(a, grid, s);
+      case DLADMM_V7_SCALAR_V1E: return launch_rs<MP, NP, EM_V1, PK_S1, true>(a, grid, s);
+    }
+    return hipErrorInvalidValue;
+  }
   switch (variant) {
     case DLADMM_V1_LENA: return launch_rs<MP, NP, EM_V1, PK_ELEM>(a, grid, s);
     case DLADMM_V2_LTHETA: return launch_rs<MP, NP, EM_V1, PK_ROW>(a, grid, s);
@@ -409,6 +432,7 @@ hipError_t launch_fused_rs(int shape, int variant, const FusedArgs& a, int grid,
     case DLADMM_V4_SCALAR: return launch_rs<MP, NP, EM_VVAR, PK_SCALAR>(a, grid, s);
     case DLADMM_V5_TIED: return launch_rs<MP, NP, EM_VVAR, PK_S1>(a, grid, s);
     case DLADMM_V6_LASSO: return launch_rs<MP, NP, EM_LASSO, PK_SCALAR>(a, grid, s);
+    case DLADMM_V7_SCALAR_V1E: return launch_rs<MP, NP, EM_V1, PK_S1>(a, grid, s);
   }
   return hipErrorInvalidValue;
 }

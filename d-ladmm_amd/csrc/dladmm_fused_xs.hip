@@ -172,7 +172,8 @@ __global__ __launch_bounds__(256, 1) void fused_xs_kernel(const FusedArgs a) {
     const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
     cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
     p.b2 = sp[DLADMM_P_BETA2];
-    p.b3 = sp[DLADMM_P_BETA3];
+    // the scalar V1 form (V7) has no beta3: L = L + beta1 T, as everywhere in EM_V1
+    p.b3 = (EMODE == EM_V1 && PKIND == PK_S1) ? sp[DLADMM_P_BETA1] : sp[DLADMM_P_BETA3];
     p.ss2 = sp[DLADMM_P_SS2];
     p.ss2b = sp[DLADMM_P_SS2B];
     p.the = shrink_params(sp[DLADMM_P_THETA_E]);
@@ -457,7 +458,7 @@ size_t xs_group_floats() {
 }
 
 hipError_t launch_fused_xs(int shape, int variant, const FusedArgs& a, hipStream_t s) {
-  if (shape != 2 || !a.xch || !a.xcnt) return hipErrorInvalidValue;
+  if (shape != 2 || !a.xch || !a.xcnt || a.elz) return hipErrorInvalidValue;
   constexpr int MP = kShapeMP[2], NP = kShapeNP[2];
   const int grid = xs_grid(a.B);
   switch (variant) {
@@ -467,6 +468,7 @@ hipError_t launch_fused_xs(int shape, int variant, const FusedArgs& a, hipStream
     case DLADMM_V4_SCALAR: return launch_xs<MP, NP, EM_VVAR, PK_SCALAR>(a, grid, s);
     case DLADMM_V5_TIED: return launch_xs<MP, NP, EM_VVAR, PK_S1>(a, grid, s);
     case DLADMM_V6_LASSO: return launch_xs<MP, NP, EM_LASSO, PK_SCALAR>(a, grid, s);
+    case DLADMM_V7_SCALAR_V1E: return launch_xs<MP, NP, EM_V1, PK_S1>(a, grid, s);
   }
   return hipErrorInvalidValue;
 }

@@ -11,7 +11,11 @@ namespace dladmm {
 struct FusedArgs {
   int m, n, B, K;
   int keep_all, loss_kind, ldl;   // ldl: columns per row of lossp (tiles * 64)
-  int pad0;
+  // DLADMM_F_ELZ (paths 1 and 5): 0 = the plain forward; 1 = K steps E, L, Z from (Z0, E0, L0)
+  // -- the prologue pass carries row 0's full E / L / T epilogue, pass G2(k) runs on the E slots
+  // of row k + 1 and writes E / L / P [k + 1], and the run ends after G1(K - 1); 2 = also a last
+  // product pass that stores only P[K] = A Z_{K-1} (DLADMM_F_ELZ_TAIL)
+  int elz;
   const float* X;  int64_t ldx;
   const float* Z0; int64_t ldz0;
   const float* E0; int64_t lde0;
@@ -54,6 +58,10 @@ hipError_t launch_fused_shape(int shape, int variant, const FusedArgs& a, int gr
 // the same kernels that also store P_k = A Z_k (a.Po) for the backward (dladmm_fused_savep.hip)
 hipError_t launch_fused_shape_savep(int shape, int variant, const FusedArgs& a, int grid,
                                     hipStream_t s);
+// the DLADMM_F_ELZ entry / exit modes of the same kernels (dladmm_fused_elz.hip; a.elz != 0):
+// V4 / V5 / V7, saved-product form (a.Po may be null)
+hipError_t launch_fused_shape_elz(int shape, int variant, const FusedArgs& a, int grid,
+                                  hipStream_t s);
 // the load-P0 form of the same kernels (dladmm_fused_p0.hip, dladmm_fused_p0_savep.hip): no
 // prologue GEMM pass, A Z0 is read from a.P0.  p0_supports: false for an instantiation left on the
 // compute form (DESIGN: none).  launch_p0_producer writes P0 [MP][ldp] = Ap Z0 with the fused

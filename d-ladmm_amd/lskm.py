@@ -32,8 +32,9 @@ _UPDATERS = {"None": _lib.MU_NONE, "EMA": _lib.MU_EMA, "GS": _lib.MU_GS, "RT": _
 
 
 class DLADMMNetLSKM(DLADMMNetScalar):
-    """test_syn_l1l1_scalar.py:73-322 (also the LSKM classes of test_syn_l1l1_newS*.py /
-    test_syn_scalar_*_Acols.py share this KM / S / safeguard machinery)."""
+    """test_syn_l1l1_scalar.py:73-322 only.  The test classes of test_syn_l1l1_newS*.py and
+    test_syn_scalar_*_Acols.py use another classic step, loop state and safeguard norm: they are
+    lskm_news.DLADMMNetNewSLSKM / DLADMMNetTiedNewSLSKM / DLADMMNetPTiedNewSLSKM."""
     WSCALE = 1.0   # :113: m.weight = A.t() + 1e-3 * randn (no 0.4)
     NAME = "DLADMMNet"
 

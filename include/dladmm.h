@@ -39,7 +39,13 @@ enum dladmm_variant {
   DLADMM_V3_FULL = 3,   /* main_syn_l1l1_full.py:16-96   per-row beta1/2/3, ss2, thetas         */
   DLADMM_V4_SCALAR = 4, /* main_syn_l1l1_scalar.py:34-131 all params (1,1)                     */
   DLADMM_V5_TIED = 5,   /* main_syn_l1l1_scalar_tied.py:34-104 shared fc, per-layer ss1       */
-  DLADMM_V6_LASSO = 6   /* main_syn_lasso_scalar.py:17-118 linear E-step                      */
+  DLADMM_V6_LASSO = 6,  /* main_syn_lasso_scalar.py:17-118 linear E-step                      */
+  DLADMM_V7_SCALAR_V1E = 7 /* test_syn_l1l1_newS.py:131-164 (KM_ZEL / KM_ELZ): the V1 E-step
+                              E = S(X - A Z - b2 L, theta_e) with scalar parameters and a step s1
+                              on W Var; slots beta1, beta2, theta_e, theta_z, s1 (b3 = beta1).
+                              Fused fp32 forward only (paths 1, 5, 6; inference: P only with
+                              DLADMM_F_ELZ, no backward, no split-f16 / bf16 / per-layer plan:
+                              DLADMM_E_UNSUPPORTED)                                               */
 };
 
 /* Per-layer objective reduced inside the kernel (the reference training loop's loss[k]). */
@@ -199,7 +205,7 @@ enum dladmm_flags {
   DLADMM_F_P0_SAVE = 512,      /* the call runs as without the flag and also leaves the packed A
                                   and P0 in the workspace for later DLADMM_F_P0_REUSE calls.  Wins
                                   over DLADMM_F_P0_REUSE when both are set                         */
-  DLADMM_F_P0_REUSE = 1024     /* the call packs no A and forms no A Z0: it reads both from the
+  DLADMM_F_P0_REUSE = 1024,    /* the call packs no A and forms no A Z0: it reads both from the
                                   workspace.  The caller's contract: `workspace` is the one a
                                   DLADMM_F_P0_SAVE call ran on (in stream order before this call)
                                   with the same variant, m, n, batch, precision, layer count and
@@ -208,6 +214,22 @@ enum dladmm_flags {
                                   strides, and nothing but dladmm_fwd_f32 calls under that same
                                   contract has written it since.  The weights, the parameters,
                                   every other input and the outputs may differ                    */
+  /* Entry half a layer later (the newS safeguarded KM loop, test_syn_l1l1_newS.py:219-234, which
+     carries the triple (E, L, Z)).  The call runs `layers` steps from the state (Z0, E0, L0), step
+     j on row j of scalar_params and on W[j]:
+       P = A Z;  E = Estep(E, L, P, X);  T = (P + E) - X;  L = L + b3 T;  Var = L + b1 T;
+       Z = S(Z - s1 (W Var), theta_z)
+     and writes E[j], L[j], Z[j] and (T != NULL) T[j]; T[layers] is not written.  The E-step is the
+     variant's (V4 / V5: the VVar form, V7: the V1 form); the caller assembles the rows (the kernel
+     knows no layer shift).  The arithmetic is the fused kernel's second product's epilogue
+     followed by its first product's pass, so a run from (Z_k, E_k-1, L_k-1) gives the bits a
+     plain call gives for the same layers.  Needs keep_all = 1, loss_kind = 0, DLADMM_PREC_F32,
+     V4 / V5 / V7 and m <= 256, n <= 512 (else DLADMM_E_UNSUPPORTED); runs on path 1 or 5 (never
+     6), ignores the P0 flags.  P (optional): P[j] = the product A Z step j consumed. */
+  DLADMM_F_ELZ = 2048,
+  /* With DLADMM_F_ELZ and P != NULL ([layers + 1][m][ld_out]): after the last step also form
+     P[layers] = A Z[layers - 1] -- what the newS safeguard norm needs (dladmm_safeguard_news_f32) */
+  DLADMM_F_ELZ_TAIL = 4096
 };
 
 /* ABI version the library was built with. */
@@ -220,7 +242,7 @@ size_t dladmm_fwd_workspace_bytes(const dladmm_fwd_desc* d);
    2 = per-layer kernel pair (large shapes, or one layer's matrix >= 2^31 bytes), 3 = per-layer
    tile kernels on bf16 operands, 4 = fused kernel on split-f16 operands (DLADMM_PREC_F32_SPLIT),
    5 = fused kernel with each workgroup's rows split over its waves (16 columns per workgroup):
-   small fp32 batches (at most three workgroups per CU) of V1 / V4 / V5 / V6 (V2 / V3 under
+   small fp32 batches (at most three workgroups per CU) of V1 / V4 / V5 / V6 / V7 (V2 / V3 under
    DLADMM_F_ROWSPLIT_ROWP) at m <= 256, n <= 512 (and m > 64 or n > 256) -- the same arithmetic as path 1, bit for bit (the fused
    objective's per-column sums: to fp32 rounding), 6 = the same split over four workgroups per
    16 columns (16 waves; the column state handed between them through the workspace once per
@@ -362,6 +384,42 @@ typedef struct dladmm_safeguard_desc {
 } dladmm_safeguard_desc;
 
 int dladmm_safeguard_f32(const dladmm_safeguard_desc* d, void* stream);
+
+/*
+ * Safeguard step of the newS scripts (test_syn_l1l1_newS.py:167-185, :236-251 and the _Acols
+ * scripts): the norm of Snorm_ELZ, the mu update and the select of the triple (E, L, Z).
+ * Snorm_ELZ runs one KM_ELZ step from the L2O candidate (El, Ll, Zl), giving (En, Znn), and takes
+ *   sqrt( sum_i (A Znn + En - X)_i^2 + d' P2 d ),  d = Znn - Zl,  P2 = I / (beta ss1) - A'A.
+ * Here d' P2 d = |d|^2 / (beta ss1) - |A d|^2 and A d = A Znn - A Zl, so with the two products a
+ * DLADMM_F_ELZ | DLADMM_F_ELZ_TAIL call of that step saved (Pn = P[0] = A Zl, Pnn = P[1] = A Znn)
+ *   r1 = sum (Pnn + En - X)^2,  dd = sum (Znn - Zl)^2,  ad = sum (Pnn - Pn)^2   (fp64, fixed order)
+ *   Snorm = sqrt(r1 + dd * inv_bs - ad),  inv_bs = 1 / (beta ss1);  keep = Snorm < (1 - delta) mu;
+ * mu is updated as in dladmm_safeguard_f32, the kept (L2O) or safeguarded (KM: Ek, Lk, Zk) triple
+ * goes to (Eo, Lo, Zo), *count grows by the safeguarded columns and mask[b] (optional) = keep.
+ * With Zo == NULL it only initialises mu = Snorm (El, Ll, Ek, Lk, Zk, count unused).
+ * Zl == Zk with keep for every column, or El == Ek, is allowed (layer 0 passes E0, L0 for both).
+ */
+typedef struct dladmm_safeguard_news_desc {
+  int32_t abi_version;
+  int32_t m, n, batch;
+  int64_t ld;
+  const float* X;
+  const float *Zl, *El, *Ll;       /* L2O candidate */
+  const float *Zk, *Ek, *Lk;       /* KM candidate */
+  const float *En, *Znn;           /* the KM_ELZ step from the L2O candidate */
+  const float *Pn, *Pnn;           /* A Zl and A Znn as that step formed them */
+  float *Zo, *Eo, *Lo;             /* selected outputs (alias no input) */
+  float* mu;                       /* [batch] in/out */
+  float* norm_out;                 /* [batch] Snorm or NULL */
+  int32_t* count;                  /* += safeguarded columns */
+  uint8_t* mask;                   /* [batch] keep decisions or NULL */
+  const float* inv_bs;             /* device scalar 1 / (beta ss1) */
+  double delta;
+  int32_t updater;                 /* enum dladmm_mu_updater */
+  float mu_param;
+} dladmm_safeguard_news_desc;
+
+int dladmm_safeguard_news_f32(const dladmm_safeguard_news_desc* d, void* stream);
 
 /*
  * Per-column evaluation objectives over saved layers: for every
