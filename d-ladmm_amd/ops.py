@@ -351,7 +351,8 @@ def dladmm_backward(variant: int, X: torch.Tensor, A: torch.Tensor, W: Sequence[
                     row_params: Optional[torch.Tensor] = None,
                     beta1_elem: Sequence[torch.Tensor] = (),
                     beta2_elem: Sequence[torch.Tensor] = (),
-                    tied: bool = False, flags: Optional[int] = None) -> BackwardResult:
+                    tied: bool = False, flags: Optional[int] = None,
+                    wgrad_split: Optional[bool] = None) -> BackwardResult:
     """Gradients of sum_k <gZ_k,Z_k> + <gE_k,E_k> + <gL_k,L_k> + sum_j <gT_j,T_j> (+ the fused
     training objective sum_k cz_k sum|Z_k| + cf_k fit_k when loss_kind, loss_coef = device
     (K, 2) fp32 (cz_k, cf_k)) w.r.t. the parameters of the forward that produced `saved` (a
@@ -359,7 +360,10 @@ def dladmm_backward(variant: int, X: torch.Tensor, A: torch.Tensor, W: Sequence[
     per-layer sequences of (rows, B) tensors (None entries / None = zero).  This is the backward
     of the reference's `total_loss.backward()` through DLADMMNet.forward
     (main_syn_l1l1_scalar.py:298).  flags: plan options; None = the forward's (saved.flags)
-    plus those of an enclosing plan_flags block."""
+    plus those of an enclosing plan_flags block.  wgrad_split: whether the weight-gradient GEMM
+    runs split-f16 (the C ABI's fwd.precision "f32_split"); None = as the forward ran, i.e. after
+    a split-f16 forward (saved.path 4) only -- the modules never pass it, so past 256 x 512,
+    where every forward is fp32, their weight gradient is the fp32-MFMA kernel's."""
     L = _lib.lib()
     if saved.T is None or saved.Z.shape[0] != len(W):
         raise ValueError("dladmm: backward needs the keep_all forward outputs including T")
@@ -383,7 +387,8 @@ def dladmm_backward(variant: int, X: torch.Tensor, A: torch.Tensor, W: Sequence[
                           beta1_elem, beta2_elem, True, 0, saved, flags)
     # a split-f16 training forward (path 4) also runs the weight-gradient GEMM on the f16
     # matrix cores (csrc/dladmm_wgrad_x3.hip); every other backward kernel is the fp32 one
-    d.fwd.precision = _PRECISIONS["f32_split"] if saved.path == 4 else _PRECISIONS["f32"]
+    split = saved.path == 4 if wgrad_split is None else bool(wgrad_split)
+    d.fwd.precision = _PRECISIONS["f32_split"] if split else _PRECISIONS["f32"]
     counts = {"gZ": (K, n), "gE": (K, m), "gL": (K, m), "gT": (K + 1, m)}
     for nm, seq in (("gZ", gZ), ("gE", gE), ("gL", gL), ("gT", gT)):
         if seq is None or all(g is None for g in seq):

@@ -98,11 +98,14 @@ def _reduce_to(g, shape):
 
 
 def vjp(variant, X, A, Z0, E0, L0, state_dict, layers, gZ=None, gE=None, gL=None, gT=None,
-        dtype=np.float32):
+        dtype=np.float32, keep=None):
     """Gradient of sum_k <gZ[k],Z_k> + <gE[k],E_k> + <gL[k],L_k> + sum_j <gT[j],T_j> w.r.t. every
     entry of `state_dict` (same keys; None-grads come back as zeros).  gZ/gE/gL: K arrays or None,
     gT: K+1 arrays or None.  The forward is recomputed here in `dtype`, op for op as the
-    reference (dladmm_oracle.forward), and the reverse sweep follows it in reverse."""
+    reference (dladmm_oracle.forward), and the reverse sweep follows it in reverse.
+    keep: a dict that receives the shrink inputs of every layer, U (Z-step) and Eh (E-step; None
+    for the LASSO E-step, which has no shrink), with their thresholds thz / the, and the
+    products P_k = A Z_k."""
     c = lambda a: np.asarray(a, dtype=dtype)  # noqa: E731
     X, A, Z0, E0, L0 = c(X), c(A), c(Z0), c(E0), c(L0)
     p = {k: c(v) for k, v in state_dict.items()}
@@ -144,6 +147,9 @@ def vjp(variant, X, A, Z0, E0, L0, state_dict, layers, gZ=None, gE=None, gL=None
         Vs.append(Var); Us.append(U); Ps.append(P); Qs.append(Q); Eh.append(eh)
         Zs.append(Z); Es.append(E); Ls.append(L); Ts.append(T)
 
+    if keep is not None:
+        keep.update(P=Ps, U=Us, Eh=Eh, thz=[q["thz"] for q, _ in prm],
+                    the=[q.get("the") for q, _ in prm])
     zero_n = np.zeros_like(Z0)
     zero_m = np.zeros_like(X)
     up = lambda seq, i, z: z if seq is None or seq[i] is None else c(seq[i])  # noqa: E731
