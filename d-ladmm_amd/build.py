@@ -8,6 +8,7 @@ dominate: ~1.5 min), then one shared library is linked.
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -47,6 +48,37 @@ UNIT_FLAGS = {u: ["-fno-slp-vectorize"] for u in UNITS
 # the split-f16 weight gradient unscales every MFMA result with VALU: MFMA results in VGPRs
 # (no v_accvgpr_read per element)
 UNIT_FLAGS["dladmm_wgrad_x3.hip"] = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+# The fused fp32 kernel keeps its whole state in registers; which instantiations take the two-slot
+# weight ring (csrc/dladmm_fused_kernel.h kRing2) rests on a register census.
+# So these units are compiled with the resource-usage remarks, and a kernel of theirs whose
+# scratch exceeds what is recorded here (bytes per lane, by the kernel's mangled template
+# arguments <MP, NP, EMODE, PKIND, SAVEP, P0LOAD, ELZ>; every other kernel: 0) fails the build.
+CENSUS_UNITS = ("dladmm_fused.hip", "dladmm_fused_savep.hip", "dladmm_fused_elz.hip",
+                "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip")
+SCRATCH_RECORD = {
+    "ILi256ELi512ELi1ELi0ELb1ELb0ELb1E": 416,   # V4, ELZ unit
+    "ILi256ELi512ELi1ELi3ELb1ELb0ELb1E": 416,   # V5, ELZ unit
+    "ILi256ELi512ELi0ELi3ELb1ELb0ELb1E": 12,    # V7, ELZ unit
+    "ILi256ELi512ELi1ELi1ELb1ELb0ELb0E": 52,    # V3, compute form with the saved product
+}
+
+
+def check_scratch(unit, remarks):
+    """Parse -Rpass-analysis=kernel-resource-usage output; raise if a fused kernel's scratch grew."""
+    name, bad = None, []
+    for line in remarks.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            continue
+        m = re.search(r"remark:\s+ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and name and "fused_kernel" in name:
+            allowed = max([v for k, v in SCRATCH_RECORD.items() if k in name] or [0])
+            if int(m.group(1)) > allowed:
+                bad.append(f"{name}: {m.group(1)} B of scratch per lane (recorded: {allowed})")
+    if bad:
+        raise RuntimeError(f"{unit}: register census exceeded (keep the instantiation on the "
+                           "four-slot ring, or record it):\n  " + "\n  ".join(bad))
 
 
 def deps(path, seen=None):
@@ -105,13 +137,26 @@ def build(force: bool = False, verbose: bool = True, extra_flags=()) -> str:
         obj = os.path.join(OBJ, u.replace(".hip", ".o"))
         objs.append(obj)
         if force or extra_flags or _stale(obj, sorted(deps(src))):
-            jobs.append([cc] + FLAGS + UNIT_FLAGS.get(u, []) + list(extra_flags) +
+            census = ["-Rpass-analysis=kernel-resource-usage"] if u in CENSUS_UNITS else []
+            jobs.append([cc] + FLAGS + UNIT_FLAGS.get(u, []) + census + list(extra_flags) +
                         ["-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:
             print("[dladmm build]", " ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
+        if "-Rpass-analysis=kernel-resource-usage" in cmd:
+            # the remarks arrive on stderr: keep them out of the log, print everything else
+            p = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
+            rest = [ln for ln in p.stderr.splitlines()
+                    if "kernel-resource-usage" not in ln and "__launch_bounds__" not in ln
+                    and ln.strip() not in ("", "| ^")]
+            if rest:
+                print("\n".join(rest), file=sys.stderr, flush=True)
+            if p.returncode:
+                raise subprocess.CalledProcessError(p.returncode, cmd)
+            check_scratch(os.path.basename(cmd[-3]), p.stderr)
+        else:
+            subprocess.run(cmd, check=True)
 
     # the long reverse-sweep units first, so they do not end up last in the pool
     jobs.sort(key=lambda c: 0 if os.path.basename(c[-3]).startswith("dladmm_reverse_") else 1)

@@ -21,8 +21,9 @@
 //    loses accuracy against the reference on cancelling residuals;
 //  * W_k and A are pre-packed (pack_frags_kernel) into paired fragment order (1 KiB per 16x16
 //    fragment = what one wave's lanes need for 4 MFMAs) and streamed from L2/MALL by
-//    LDS-DMA into a 3-slot LDS ring shared by the 4 waves (one chunk read, one landed, one in
-//    flight), so the next chunk's first fragments are read ahead before the current one ends;
+//    LDS-DMA into an LDS ring shared by the 4 waves (dladmm_ring_windows.h: two slots of 32
+//    fragments, each refilled piece by piece over the steps after the barrier that ends its
+//    chunk), so the next chunk's first fragments are read ahead before the current one ends;
 //  * each pair's epilogue (shrink, E/L/T/Var updates, HBM stores, objective partial sums) is
 //    cut into its 8 rows and spread over the MFMA steps of the next pair.
 // Elementwise arithmetic is compiled with -ffp-contract=off; a uniform-threshold shrink uses
@@ -33,6 +34,7 @@
 
 #include "dladmm_common.h"
 #include "dladmm_internal.h"
+#include "dladmm_ring_windows.h"
 
 #ifndef DLADMM_ABLATE
 #define DLADMM_ABLATE 0  // timing experiments only, see tools/ablate.py
@@ -41,21 +43,8 @@
 #define DLADMM_ABL_AUX 0
 #endif
 #ifndef DLADMM_STAMP
-#define DLADMM_STAMP 0  // diagnostic build: per-wave cycle sums of the passes and ring barriers
-#endif
-#ifndef DLADMM_SLOTS
-#define DLADMM_SLOTS 4  // weight ring slots (chunks in flight: slots - 1); the per-row kinds
-                        // (their parameter tables take 24 KiB of LDS) use at most 4
-#endif
-#ifndef DLADMM_CNT
-#define DLADMM_CNT 1  // ring barriers of every variant wait with counted vmcnt (else only V1)
-#endif
-#ifndef DLADMM_CHUNK
-#define DLADMM_CHUNK 16
-#endif
-#ifndef DLADMM_DMA_LATE
-#define DLADMM_DMA_LATE 0  // ring LDS-DMA group issued after the barrier step's MFMAs instead of
-                           // beside its fragment reads (A/B; the ring windows count accordingly)
+#define DLADMM_STAMP 0  // diagnostic build: per-wave cycle sums of the passes and ring barriers;
+                        // 2: also the chunk-boundary step in parts (32 sums per wave, below)
 #endif
 #ifndef DLADMM_VR_AGPR
 #define DLADMM_VR_AGPR 1  // Var pinned to AGPRs (0: the compiler places it; A/B experiment)
@@ -73,97 +62,25 @@
 
 namespace dladmm {
 
-template <int MP, int NP, int EMODE, int PKIND>
+template <int MP, int NP, int EMODE, int PKIND, bool ALLOW2 = true>
 struct Fused {
   static constexpr int MB = MP / 16;
   static constexpr int NB = NP / 16;
   static constexpr int GF = MB * NB;                // fragments per GEMM
-  static constexpr int CF = GF < DLADMM_CHUNK ? GF : DLADMM_CHUNK;  // fragments per ring chunk
-  static constexpr int NCH = GF / CF;               // chunks per GEMM
+  using R = RingSched<GF, PKIND, ALLOW2>;           // ring geometry and piece schedule
+  static_assert(kWinPkRow == PK_ROW && kWinPkElem == PK_ELEM, "dladmm_ring_windows.h");
+  static constexpr int CF = R::CF;                  // fragments per ring chunk
+  static constexpr int NCH = R::NCH;                // chunks per GEMM
   static constexpr int TAB = ((6 * MP + NP + 63) / 64) * 64;  // per-row param table (floats,
                                                               // whole 64-entry DMA pieces)
-  static constexpr int SLOTS = (PKIND == PK_ROW && DLADMM_SLOTS > 4) ? 4 : DLADMM_SLOTS;
+  static constexpr int SLOTS = R::SLOTS;
   static constexpr int RING_F4 = SLOTS * CF * 64;  // ring slots of CF fragments
-  static_assert(SLOTS >= 3, "the ring needs one slot being read, one landed, one in flight");
   static constexpr int TAB_F4 = (PKIND == PK_ROW) ? (3 * TAB) / 4 : 0;  // 3 layer buffers
   static constexpr int X_F4 = kWaves * MB * 64;     // the tile's X, resident in LDS
   static_assert(MB % 2 == 0 && NB % 2 == 0, "output blocks are processed in pairs");
   static_assert(GF % CF == 0 && CF % 2 == 0, "chunking");
   static_assert(TAB % 4 == 0, "table alignment");
   static_assert((RING_F4 + X_F4 + TAB_F4) * 16 <= 160 * 1024, "LDS budget");
-};
-
-// pending epilogue row i (0..7: block half i/4, row i%4) runs at step (i * SP) / 8 of a pair of
-// SP steps
-constexpr bool rows_at(int step, int SP, int i) { return (i * SP) / 8 == step; }
-
-// Static VM-operation windows of the ring barriers (V1 / PK_ELEM: its 24 beta loads per G2 pair
-// would otherwise be drained by the vmcnt(0) of the next barrier, one chunk after issue).  A
-// barrier at step s (the last step of a chunk of SPC steps) waits for the chunk DMA issued at
-// the previous barrier step s - SPC; every store and beta load issued in the bodies of steps
-// s - SPC .. s - 1 (the barrier step's own body follows its head) is newer.  Counted: the
-// stores of the epilogue rows (always issued; out-of-range ones go to 0-record buffers) and the
-// beta prefetch at each G2 pair start.  Not counted (conditional): the per-column objective
-// stores -- counting too few only waits longer.  Other variants return 0 (plain vmcnt(0)).
-template <int MB, int NB, int CF, int PKIND, bool SAVEP>
-struct WinCount {
-  static constexpr int ST2 = SAVEP ? 4 : 3;  // stores of a G2 row: E, L, T (+ P)
-  static constexpr int SPC = CF / 2;  // steps per chunk
-  static constexpr int rows_in(int step, int SP) {
-    int c = 0;
-    for (int i = 0; i < 8; ++i) c += ((i * SP) / 8 == step) ? 1 : 0;
-    return c;
-  }
-  // VM operations issued in the body of step t of a G1 / G2 pass
-  static constexpr int ops1(int t) {
-    return rows_in(t % MB, MB) * (t / MB == 0 ? ST2 : 1);  // pair 0 runs G2 rows (E, L, T)
-  }
-  // step of the pair that issues beta-prefetch part `part` (3 loads)
-  static constexpr int part_step(int part) { return (part * NB) / 16; }
-  static constexpr int parts_at(int kb) {
-    int c = 0;
-    for (int q = 0; q < 8; ++q) c += part_step(q) == kb ? 1 : 0;
-    return c;
-  }
-  static constexpr int ops2(int t, bool pro) {
-    const int p = t / NB, kb = t % NB;
-    constexpr int pf = PKIND == PK_ELEM ? 3 : 0;  // beta loads per prefetch part
-    if (p == 0) return (pro ? 0 : rows_in(kb, NB)) + pf * parts_at(kb);  // G1 rows + prefetch
-    return (ST2 + pf) * rows_in(kb, NB);  // G2 rows (E, L, T stores) + a prefetch part each
-  }
-  static constexpr int T1 = (NB / 2) * MB, T2 = (MB / 2) * NB;  // steps of a G1 / G2 pass
-  // With S slots the awaited chunk's DMA was issued S-2 barriers back: the bodies of the
-  // (S-2)*SPC steps since and the DMA groups of the S-3 chunks issued after it are newer.  A
-  // step before the pass counts with the previous pass's schedule (the smaller of the two
-  // possible previous passes before G1; nothing before the prologue).
-  static constexpr int SLOTS = (PKIND == PK_ROW && DLADMM_SLOTS > 4) ? 4 : DLADMM_SLOTS;
-  static constexpr int WSTEPS = (SLOTS - 2) * SPC;
-  // DMA_LATE: the awaited group was issued after its step's body, so that body is older
-  static constexpr int W0 = DLADMM_DMA_LATE ? 1 : 0;
-  static constexpr int DMAG = (SLOTS - 3) * ((CF + 3) / 4);
-  template <int S>
-  static constexpr int g1() {
-    if constexpr ((PKIND != PK_ELEM && !DLADMM_CNT) || S % SPC != SPC - 1) return 0;
-    int n = DMAG;
-    for (int t = S - WSTEPS + W0; t < S; ++t) {
-      if (t >= 0) n += ops1(t);
-      else if (T2 + t >= 0) {
-        const int a = ops2(T2 + t, true), b = ops2(T2 + t, false);
-        n += a < b ? a : b;
-      }
-    }
-    return n < 63 ? n : 63;
-  }
-  template <int S, bool PRO>
-  static constexpr int g2() {
-    if constexpr ((PKIND != PK_ELEM && !DLADMM_CNT) || S % SPC != SPC - 1) return 0;
-    int n = DMAG;
-    for (int t = S - WSTEPS + W0; t < S; ++t) {
-      if (t >= 0) n += ops2(t, PRO);
-      else if (!PRO && T1 + t >= 0) n += ops1(T1 + t);
-    }
-    return n < 63 ? n : 63;
-  }
 };
 
 // SAVEP: also store P_k = A Z_k (a.Po) for the backward's BK1 (training forwards only: the
@@ -181,9 +98,16 @@ struct WinCount {
 template <int MP, int NP, int EMODE, int PKIND, bool SAVEP, bool P0LOAD = false, bool ELZ = false>
 __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   static_assert(!(P0LOAD && ELZ), "the ELZ entry computes its own prologue product");
-  using F = Fused<MP, NP, EMODE, PKIND>;
+  // The two-slot ring (DLADMM_RING2) is for the scalar-parameter kinds' compute, load and
+  // saved-product forms (V4 / V5 / V6 / V7): V4 measured 1.2 % faster, V6 equal.  Kept on the
+  // four-slot ring: V1, which measured 1 % slower with it; V2, not measured; V3 and the ELZ
+  // units, which at 256 x 512 have no register left for its bookkeeping and would add scratch
+  // (d-ladmm_amd/build.py checks every fused kernel's scratch against the recorded census).
+  constexpr bool kRing2 = (PKIND == PK_SCALAR || PKIND == PK_S1) && !ELZ;
+  using F = Fused<MP, NP, EMODE, PKIND, kRing2>;
   constexpr int MB = F::MB, NB = F::NB, CF = F::CF, NCH = F::NCH, TAB = F::TAB;
-  using Win = WinCount<MB, NB, CF, PKIND, SAVEP>;
+  using Win = WinCount<MB, NB, CF, PKIND, SAVEP, kRing2>;
+  using R = typename F::R;
   __shared__ f32x4 smem[F::RING_F4 + F::X_F4 + F::TAB_F4];
   f32x4* ring = smem;
   f32x4* xs = smem + F::RING_F4;  // xs[w][b][lane] = X rows 16b+4g+0..3 of this lane's column
@@ -248,6 +172,28 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
         if (CF % 4 == 0 || f < CF) glds16(base + f * kFrag, lane * 16, dst + f * 64);
       }
     }
+  };
+  // spread form: piece i of this wave (fragment 4i + w) of the chunk at base -> slot
+  auto issue_piece = [&](const float* base, int slot, int i) {
+#if DLADMM_ABLATE & 1
+    if (base != a.Ap) return;
+#endif
+    const int f = 4 * i + w;
+    glds16(base + f * kFrag, lane * 16, ring + (slot * CF + f) * 64);
+  };
+  // spread form: source and slot of the chunk whose pieces are being issued, this wave's stagger
+  [[maybe_unused]] const float* pbase = nullptr;
+  [[maybe_unused]] int pslot = 0;
+  [[maybe_unused]] const int stag = R::SMAX > 0 ? R::stag(w) : 0;
+  // Priming of the spread form, from GEMM gi on: the first AH - 1 chunks, and of chunk AH - 1
+  // only the piece of offset 0 -- the priming stands in for the barrier step before step 0, and
+  // the first steps issue that chunk's other pieces like any chunk's.
+  auto prime_spread = [&](int gi) {
+#pragma unroll
+    for (int c = 0; c < R::AH - 1; ++c) issue(chunk_src(gi, c), c);
+    pbase = chunk_src(gi, R::AH - 1);
+    pslot = (R::AH - 1) % F::SLOTS;
+    if (stag == 0) issue_piece(pbase, pslot, 0);
   };
   auto slot_add = [](int s, int d) -> int {
     s += d;
@@ -319,8 +265,12 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
     if constexpr (P0LOAD) {
       // the ring priming depends on nothing: first.  Z0 is loaded after the priming barrier
       // (below), so that the barrier's vmcnt(0) does not wait for it.
+      if constexpr (R::SPREAD) {
+        prime_spread(1);
+      } else {
 #pragma unroll
-      for (int c = 0; c < F::SLOTS - 1; ++c) issue(chunk_src(1, c), c);
+        for (int c = 0; c < R::AH; ++c) issue(chunk_src(1, c), c);
+      }
     } else {
 #pragma unroll
       for (int b = 0; b < NB; ++b)
@@ -562,8 +512,16 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   uint64_t st_vm = 0, st_bar = 0, st_g1 = 0, st_g2 = 0;
   const uint64_t st_0 = stamp();
 #endif
-  auto step_head = [&](auto S_, int gi, auto WIN_) {
+#if DLADMM_STAMP == 2
+  // The boundary step in parts, by class c = 2 * (G2 pass) + (the step runs an epilogue row):
+  // st2[4 c + 0..3] = vmcnt wait | s_barrier | barrier exit to the end of the DMA issue (head
+  // form: the whole group; late and spread forms: their issue after the MFMAs) | the rest of the
+  // step.  st_sp[G2 pass] = issue of the spread pieces in the steps that hold no barrier.
+  uint64_t st2[16] = {}, st_sp[2] = {}, st_t3 = 0;
+#endif
+  auto step_head = [&](auto S_, int gi, auto WIN_, auto CLS_) {
     constexpr int s = decltype(S_)::value;
+    [[maybe_unused]] constexpr int cls = decltype(CLS_)::value;
     constexpr int WIN = decltype(WIN_)::value;
     constexpr int fi = 2 * s, fc = fi % CF, ch = fi / CF;
     if constexpr (fc + 2 < CF) {
@@ -585,32 +543,80 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
       if constexpr (WIN > 0) ring_barrier_cnt<WIN>();
       else ring_barrier();
 #endif
-      if constexpr (!DLADMM_DMA_LATE)
-        issue(chunk_src(gi, ch + F::SLOTS - 1), slot_add(cur, F::SLOTS - 1));
+      if constexpr (!R::LATE && !R::SPREAD)
+        issue(chunk_src(gi, ch + R::AH), slot_add(cur, R::AH));
+#if DLADMM_STAMP == 2
+      __builtin_amdgcn_sched_barrier(0);
+      st_t3 = stamp();
+      __builtin_amdgcn_sched_barrier(0);
+      st2[4 * cls + 0] += t1 - t0;
+      st2[4 * cls + 1] += t2 - t1;
+      st2[4 * cls + 2] += st_t3 - t2;
+#endif
       const int nx = slot_add(cur, 1);
       fr[(fi + 2) % 4] = frag(nx, 0);
       fr[(fi + 3) % 4] = frag(nx, 1);
     }
   };
-  auto step_tail = [&](auto S_, int gi) {
+  auto step_tail = [&](auto S_, int gi, auto CLS_) {
     constexpr int s = decltype(S_)::value;
+    [[maybe_unused]] constexpr int cls = decltype(CLS_)::value;
     constexpr int fi = 2 * s, fc = fi % CF, ch = fi / CF;
     __builtin_amdgcn_sched_barrier(0);
+#if DLADMM_STAMP == 2
+    uint64_t ta = 0;
+    constexpr bool piece_step = R::SPREAD && (fc + 2 >= CF ? 0 : fc / 2 + 1) <= R::OLAST;
+    if constexpr (fc + 2 >= CF || piece_step) {
+      ta = stamp();
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (fc + 2 >= CF) st2[4 * cls + 3] += ta - st_t3;
+    }
+#endif
     if constexpr (fc + 2 >= CF) {
-      if constexpr (DLADMM_DMA_LATE) {
+      if constexpr (R::LATE) {
         // after the step's MFMAs (an LDS-DMA instruction issues cheaper among MFMAs than beside
         // ds_reads, MI355X_MICROARCH.md); the barrier at this step's head freed the slot
-        issue(chunk_src(gi, ch + F::SLOTS - 1), slot_add(cur, F::SLOTS - 1));
+        issue(chunk_src(gi, ch + R::AH), slot_add(cur, R::AH));
         __builtin_amdgcn_sched_barrier(0);
       }
-      cur = slot_add(cur, 1);
     }
+    if constexpr (R::SPREAD) {
+      // after the step's MFMAs, away from the fragment reads of the heads: the piece of offset
+      // o from the last barrier step (o = 0: this step, whose barrier freed the slot)
+      constexpr int o = (fc + 2 >= CF) ? 0 : fc / 2 + 1;
+      if constexpr (o == 0) {
+        pbase = chunk_src(gi, ch + R::AH);
+        pslot = slot_add(cur, R::AH);
+      }
+      if constexpr (o <= R::OLAST) {
+        if constexpr (R::SMAX == 0) {
+          if constexpr (o < R::NPC) issue_piece(pbase, pslot, o);
+        } else {
+          const int i = o - stag;  // wave-uniform
+          if (i >= 0 && i < R::NPC) issue_piece(pbase, pslot, i);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+#if DLADMM_STAMP == 2
+    if constexpr (fc + 2 >= CF) {
+      if constexpr (R::LATE || R::SPREAD) st2[4 * cls + 2] += stamp() - ta;
+    } else if constexpr (piece_step) {
+      st_sp[cls / 2] += stamp() - ta;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    if constexpr (fc + 2 >= CF) cur = slot_add(cur, 1);
   };
 
-  // prime the ring: the first SLOTS - 1 chunks, then the first step's fragments
+  // prime the ring: the first AH chunks, then the first step's fragments
   if constexpr (!P0LOAD) {
+    if constexpr (R::SPREAD) {
+      prime_spread(0);
+    } else {
 #pragma unroll
-    for (int c = 0; c < F::SLOTS - 1; ++c) issue(chunk_src(0, c), c);
+      for (int c = 0; c < R::AH; ++c) issue(chunk_src(0, c), c);
+    }
   }
   ring_barrier();
   fr[0] = frag(0, 0);
@@ -645,8 +651,9 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
       static_for<MB>([&](auto J_) {
         constexpr int jb = decltype(J_)::value;
         constexpr int s = p * MB + jb;
+        using Cls = std::integral_constant<int, Win::rows_in(jb, MB) ? 1 : 0>;  // stamps
         step_head(std::integral_constant<int, s>{}, gi,
-                  std::integral_constant<int, Win::template g1<s>()>{});
+                  std::integral_constant<int, Win::template g1<s>()>{}, Cls{});
         static_for<8>([&](auto I_) {
           constexpr int i = decltype(I_)::value;
           constexpr int h = i / 4, r = i % 4;
@@ -669,7 +676,7 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
         cb = mfma4(wb.z, Vr[jb][2], cb);
         ca = mfma4(wa.w, Vr[jb][3], ca);
         cb = mfma4(wb.w, Vr[jb][3], cb);
-        step_tail(std::integral_constant<int, s>{}, gi);
+        step_tail(std::integral_constant<int, s>{}, gi, Cls{});
       });
       qa = ca;
       qb = cb;
@@ -694,8 +701,10 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
       static_for<NB>([&](auto K_) {
         constexpr int kb = decltype(K_)::value;
         constexpr int s = p * NB + kb;
+        using Cls = std::integral_constant<  // stamps
+            int, 2 + ((p > 0 || !PRO) && Win::rows_in(kb, NB) ? 1 : 0)>;
         step_head(std::integral_constant<int, s>{}, gi,
-                  std::integral_constant<int, Win::template g2<s, PRO>()>{});
+                  std::integral_constant<int, Win::template g2<s, PRO>()>{}, Cls{});
         if constexpr (p == 0) {
           static_for<8>([&](auto PT_) {
             constexpr int part = decltype(PT_)::value;
@@ -734,7 +743,7 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
         ca = mfma4(wa.w, Zr[kb][3], ca);
         cb = mfma4(wb.w, Zr[kb][3], cb);
 #endif
-        step_tail(std::integral_constant<int, s>{}, gi);
+        step_tail(std::integral_constant<int, s>{}, gi, Cls{});
       });
 #if DLADMM_G2_CHAINS == 2
       qa = ca + ca2;
@@ -860,13 +869,24 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if DLADMM_STAMP
   const uint64_t st_end = stamp();
-  if (a.dbg && lane < 8) {  // vector stores: lane i writes sum i
-    const uint64_t v[8] = {st_end - st_0, st_g1, st_g2, 0, st_vm, st_bar, st_primed - st_0,
-                           st_pro - st_primed};
+#if DLADMM_STAMP == 2
+  constexpr int kSums = 32;
+#else
+  constexpr int kSums = 8;
+#endif
+  if (a.dbg && lane < kSums) {  // vector stores: lane i writes sum i
+    uint64_t v[kSums] = {st_end - st_0, st_g1, st_g2, 0, st_vm, st_bar, st_primed - st_0,
+                         st_pro - st_primed};
+#if DLADMM_STAMP == 2
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[8 + i] = st2[i];
+    v[24] = st_sp[0];
+    v[25] = st_sp[1];
+#endif
     uint64_t x = 0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) x = lane == i ? v[i] : x;
-    a.dbg[((int64_t)blockIdx.x * kWaves + w) * 8 + lane] = x;
+    for (int i = 0; i < kSums; ++i) x = lane == i ? v[i] : x;
+    a.dbg[((int64_t)blockIdx.x * kWaves + w) * kSums + lane] = x;
   }
 #endif
 }
