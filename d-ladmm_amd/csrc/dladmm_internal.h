@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dladmm_common.h"
 
 namespace dladmm {
@@ -52,6 +54,23 @@ struct FusedArgs {
 constexpr int kNumShapes = 3;
 constexpr int kShapeMP[kNumShapes] = {32, 64, 256};
 constexpr int kShapeNP[kNumShapes] = {32, 256, 512};
+
+// variant -> the (EMODE, PKIND) template arguments of the fused forward kernels: returns
+// f(integral_constant EMODE, integral_constant PKIND), or hipErrorInvalidValue
+template <class F>
+hipError_t with_variant_modes(int variant, F&& f) {
+  using std::integral_constant;
+  switch (variant) {
+    case DLADMM_V1_LENA: return f(integral_constant<int, EM_V1>{}, integral_constant<int, PK_ELEM>{});
+    case DLADMM_V2_LTHETA: return f(integral_constant<int, EM_V1>{}, integral_constant<int, PK_ROW>{});
+    case DLADMM_V3_FULL: return f(integral_constant<int, EM_VVAR>{}, integral_constant<int, PK_ROW>{});
+    case DLADMM_V4_SCALAR: return f(integral_constant<int, EM_VVAR>{}, integral_constant<int, PK_SCALAR>{});
+    case DLADMM_V5_TIED: return f(integral_constant<int, EM_VVAR>{}, integral_constant<int, PK_S1>{});
+    case DLADMM_V6_LASSO: return f(integral_constant<int, EM_LASSO>{}, integral_constant<int, PK_SCALAR>{});
+    case DLADMM_V7_SCALAR_V1E: return f(integral_constant<int, EM_V1>{}, integral_constant<int, PK_S1>{});
+  }
+  return hipErrorInvalidValue;
+}
 
 hipError_t launch_fused_shape(int shape, int variant, const FusedArgs& a, int grid,
                               hipStream_t s);

@@ -5,9 +5,8 @@
 
 namespace dladmm {
 
-size_t rev_xs_group_floats() {
-  return (size_t)(kShapeNP[2] / 16 + kShapeMP[2] / 16) * 64 * 4;
-}
+// a group's exchange buffer: the gU and gP blocks
+size_t rev_xs_group_floats() { return (size_t)(kXsNB + kXsMB) * 64 * 4; }
 
 hipError_t launch_reverse_xs(int shape, int variant, const RevArgs& a, hipStream_t s) {
   if (!reverse_rs_supports(shape, variant) || !a.xch || !a.xcnt) return hipErrorInvalidValue;

@@ -1,6 +1,6 @@
 // dladmm_reverse_rs_kernel.h -- the reverse-sweep backward for SMALL batches: one workgroup per 16
 // batch columns, the ROWS of every product split over its 4 waves (the backward twin of
-// dladmm_fused_rs.hip, path 5).
+// dladmm_fused_rs_kernel.h, path 5).
 //
 // The reverse sweep (dladmm_reverse_kernel.h) gives each wave 16 columns and all rows, so the
 // reference training loops' batches of 20 / 25 (main_lena.py:155, main_syn_l1l1_scalar.py -bs
@@ -26,24 +26,20 @@
 // Instantiated by dladmm_reverse_rs.hip (V1 / V4 / V5 / V6, and the dispatch) and
 // dladmm_reverse_rs_v2.hip / _v3.hip (one translation unit each: the build stays parallel).
 #pragma once
-#include "dladmm_internal.h"
+#include "dladmm_group_xchg.h"
 
 #ifndef RRS_PF
 #define RRS_PF 4  // weight-fragment read-ahead (MFMA steps) per wave
 #endif
-#ifndef RRS_SPIN
-#define RRS_SPIN (1 << 22)  // bound of every hand-off poll (bwd path 3)
-#endif
 
 namespace dladmm {
-
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 // MEM: workgroups per 16-column group.  1 = the one-workgroup form (bwd path 2); 4 = bwd path 3,
 // after a path-6 forward: wave v = 4 member + w of the group's 16 owns G1' pair v and G2' block v
 // (half of an M_k^T pair), and the B operands (gU_k, gP_k) go between the members through the
-// group's exchange buffer once per product, by dladmm_fused_xs.hip's hand-off (sc1 stores, one
-// agent-scope counter add per member, one bounded sc1 poll; NaN adjoints after a timeout)
+// group's exchange buffer once per product, by the forward's hand-off (dladmm_group_xchg.h: sc1
+// stores, one agent-scope counter add per member, one bounded sc1 poll; NaN adjoints after a
+// timeout)
 template <int MP, int NP, int EMODE, bool GZ, bool COT, int MEM, bool ROWP = false>
 __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
   constexpr int MB = MP / 16, NB = NP / 16;
@@ -56,14 +52,13 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
   constexpr bool kV1 = EMODE == EM_V1 && !ROWP;  // V1: per-sample betas and their gradients
   static_assert(!ROWP || EMODE != EM_LASSO, "per-row parameters: V2 (EM_V1), V3 (EM_VVAR)");
   // weight-fragment read-ahead: deeper in the four-workgroup form, whose waves wait on the
-  // weight stream rather than on their MFMAs (dladmm_fused_xs.hip)
+  // weight stream rather than on their MFMAs (the forward's XS_PF)
   constexpr int PF = MEM > 1 ? 8 : RRS_PF;
   __shared__ f32x4 gpx[MB * 64];  // gP_k of the 16 columns (G1''s B operand)
   __shared__ f32x4 gux[NB * 64];  // gU_k (G2''s B operand)
 
-  const int xb = blockIdx.x;
-  const int grp = MEM == 1 ? xb : (xb >> 5) * 8 + (xb & 7);  // members share xb % 8 (one XCD)
-  const int mem = MEM == 1 ? 0 : (xb >> 3) & 3;
+  GroupXchg<MEM> X;
+  const int grp = X.grp, mem = X.mem;
   if (MEM > 1 && grp * 16 >= a.B) return;   // a padding group: every member leaves
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -84,53 +79,11 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
   const uint32_t mbytes = (uint32_t)(ml * 4);
   const int b1o = v * NB4, b2o = v * MB4;
   const rsrc_t none = mkrsrc(nullptr, 0u);
-  // MEM = 4: the group's exchange buffer (gU blocks [NB][64] f32x4, then gP blocks [MB][64]) and
-  // its hand-off counter; MEM = 1: a workgroup barrier
-  __shared__ int xerr;  // sticky: a hand-off timed out
-  if (threadIdx.x == 0) xerr = 0;
-  bool bad = false;
-  auto fin = [&](float x) -> float { return bad ? __builtin_nanf("") : x; };
+  // MEM = 4: the group's exchange buffer (gU blocks [NB][64] f32x4, then gP blocks [MB][64])
   const f32x4* xu = (const f32x4*)(MEM > 1 ? a.xch + (int64_t)grp * a.xstride : nullptr);
   const rsrc_t rxu = mkrsrc((const float*)xu, MEM > 1 ? (uint32_t)(NB * 64 * 16) : 0u);
   const rsrc_t rxp = mkrsrc((const float*)(xu + NB * 64), MEM > 1 ? (uint32_t)(MB * 64 * 16) : 0u);
-  unsigned* cnt = MEM > 1 ? a.xcnt + grp * 64 : nullptr;
-  unsigned hand = 0;
-  auto xstore = [&](const rsrc_t& rb, int blk, const f32x4& val) {
-    if constexpr (MEM > 1)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, val), rb,
-                                             (blk * 64 + lane) * 16, 0, 16);
-  };
-  auto handoff = [&](const rsrc_t& rb, f32x4* dst, auto NBLK_) {
-    if constexpr (MEM == 1) {
-      __syncthreads();
-    } else {
-      constexpr int nblk = decltype(NBLK_)::value;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      hand += MEM;
-      if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int it = 0;
-        unsigned c = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (c < hand && ++it < RRS_SPIN) {
-          __builtin_amdgcn_s_sleep(1);
-          c = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (c < hand) xerr = 1;
-      }
-      __syncthreads();
-      bad = __builtin_amdgcn_readfirstlane(xerr) != 0;
-      constexpr int per = nblk * 64 / 256;
-      f32x4 t[per];
-#pragma unroll
-      for (int q = 0; q < per; ++q)
-        t[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                             rb, (threadIdx.x + 256 * q) * 16, 0, 16));
-#pragma unroll
-      for (int q = 0; q < per; ++q) dst[threadIdx.x + 256 * q] = t[q];
-      __syncthreads();
-    }
-  };
+  X.join(a.xcnt);
   // a wave-uniform (pointer, size) buffer view (readfirstlane: the selects stay in SGPRs)
   auto urs = [](const float* p, uint32_t bytes) -> rsrc_t {
     const uint64_t v = (uint64_t)p;
@@ -171,7 +124,7 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
     if constexpr (kV1 || ROWP) return;  // V1: per-sample betas (element gradients), fixed
                                         // thresholds; V2 / V3: per-row partials (pstore)
     const float s = wave_sum(v);
-    if (lane == 0) a.part[((int64_t)layer * DLADMM_NSCALAR + slot) * a.ncg + cg] = fin(s);
+    if (lane == 0) a.part[((int64_t)layer * DLADMM_NSCALAR + slot) * a.ncg + cg] = X.fin(s);
   };
   auto flush_bk1 = [&](int j) {
     if constexpr (kV1 || ROWP) return;
@@ -234,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
   // l & 15 == 0; NaN after a timed-out hand-off, as every value formed from exchanged operands
   auto pstore = [&](rsrc_t rp, int slot, int b, int r, float v) {
     const uint32_t so = __builtin_amdgcn_readfirstlane((uint32_t)(slot * pslot * 4));
-    bstore_s(rp, vpr, so + row_off(b, r, ldp4), fin(row16_sum(v)));
+    bstore_s(rp, vpr, so + row_off(b, r, ldp4), X.fin(row16_sum(v)));
   };
 
   const uint32_t vf = (uint32_t)(lane * 16);
@@ -313,11 +266,11 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
           if constexpr (ROWP) pstore(rpk1, DLADMM_P_THETA_Z, b1o + lb, r, gb - ga);
           else psz += gb - ga;
           AZ[lb][r] = gU;
-          gu4[r] = fin(gU);
+          gu4[r] = X.fin(gU);
           bstore_s(rg, vw, row_off(b1o + lb, r, ldw4), gu4[r]);
         }
         gux[(b1o + lb) * 64 + lane] = gu4;
-        xstore(rxu, b1o + lb, gu4);
+        X.xstore(rxu, b1o + lb, lane, gu4);
       });
     });
     flush(k, DLADMM_P_THETA_Z, psz);
@@ -596,7 +549,7 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
           if constexpr (MODE == 0) psb1 += gVar * t;  // beta1 of layer k: gVar * T_k
           ps[0] += p3; ps[1] += p2; ps[2] += pe; ps[3] += ps2; ps[4] += ps2b;
         }
-        gp4[r] = fin(gP);
+        gp4[r] = X.fin(gP);
         AL[lb][r] = gLp;
         // Var of layer k: L_{k-1} + beta1_k T_k from the recomputed values (the prologue's,
         // layer K, runs past the workspace: dropped)
@@ -608,7 +561,7 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
       }
       if constexpr (MODE != 1) {
         gpx[(b2o + lb) * 64 + lane] = gp4;
-        xstore(rxp, b2o + lb, gp4);
+        X.xstore(rxp, b2o + lb, lane, gp4);
       }
     }
     });
@@ -619,18 +572,18 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
   constexpr auto kMB = std::integral_constant<int, MB>{};
   g2_pass(std::integral_constant<int, 2>{}, K);
   flush_bk1(K - 1);
-  handoff(rxp, gpx, kMB);  // gP_{K-1} complete
+  X.handoff(rxp, gpx, kMB);  // gP_{K-1} complete
   for (int k = K - 1; k >= 1; --k) {
     g1_pass(k);
-    handoff(rxu, gux, kNB);  // gU_k complete; every wave is done reading gP_k
+    X.handoff(rxu, gux, kNB);  // gU_k complete; every wave is done reading gP_k
     g2_pass(std::integral_constant<int, 0>{}, k);
     flush(k, DLADMM_P_BETA1, psb1);
     psb1 = 0.f;
     flush_bk1(k - 1);
-    handoff(rxp, gpx, kMB);  // gP_{k-1} complete; every wave is done reading gU_k
+    X.handoff(rxp, gpx, kMB);  // gP_{k-1} complete; every wave is done reading gU_k
   }
   g1_pass(0);
-  handoff(rxu, gux, kNB);
+  X.handoff(rxu, gux, kNB);
   g2_pass(std::integral_constant<int, 1>{}, 0);
   flush(0, DLADMM_P_BETA1, psb1);
 }

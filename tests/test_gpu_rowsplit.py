@@ -1,8 +1,8 @@
 """Paths 5 and 6, the small-batch row-split forms of the fused forward: path 5
-(csrc/dladmm_fused_rs.hip) a workgroup per 16 batch columns, each product's output rows split
-over its 4 waves; path 6 (csrc/dladmm_fused_xs.hip) four workgroups per 16 columns, the rows over
-their 16 waves, the column state handed between the workgroups through global memory once per
-product.  Each test runs both: split "xs" = the default plan (path 6 where its grid fits one
+(csrc/dladmm_fused_rs_kernel.h, MEM = 1) a workgroup per 16 batch columns, each product's output
+rows split over its 4 waves; path 6 (the same kernel, MEM = 4) four workgroups per 16 columns, the
+rows over their 16 waves, the column state handed between the workgroups through global memory
+once per product (csrc/dladmm_group_xchg.h).  Each test runs both: split "xs" = the default plan (path 6 where its grid fits one
 workgroup per CU, B <= 1,024 on 256 CUs), "rs" = plan flag no_xsplit (path 5).
 
 It performs the fused kernel's arithmetic operation for operation, so its outputs must equal
@@ -35,7 +35,7 @@ def _cus():
 
 
 def _xs_grid(B):
-    """dladmm_fused_xs.hip xs_grid: four workgroups per 16-column group, groups padded to 8."""
+    """csrc/dladmm_fused_xs.hip xs_grid: four workgroups per 16-column group, groups padded to 8."""
     groups = -(-B // 16)
     return -(-groups // 8) * 8 * 4
 
@@ -289,3 +289,44 @@ def test_rowsplit_reverse_sweep_cotangents(variant, kind, B, cot, split, dl):
         gs_r, gs_c = rs.g_scalar.cpu().numpy(), cl.g_scalar.cpu().numpy()
         for k in range(K):
             assert nrel(gs_r[k], gs_c[k]) <= PSLOT_TOL, (k, gs_r[k], gs_c[k])
+
+
+def test_rowsplit_elz_v5(dl):
+    """The ELZ entry (plan flag DLADMM_F_ELZ) of V5 on path 5, the one row-split instantiation no
+    other test launches (tests/test_gpu_news_lskm.py runs V4's and V7's): K = 3 steps at B = 17
+    (two 16-column groups, the second with one valid column), with and without the tail product,
+    every state bit-equal to path 1's.  An ELZ call carries no fused objective."""
+    ops, L = dl.ops, dl._lib
+    m, n, K, B = 250, 500, 3, 17
+    d = dict(variant="v5", m=m, n=n, B=B, K=K, seed=5800, perturb=0.2,
+             wscale=P.VARIANT_SPECS["v5"]["wscale"])
+    inp, sd = P.build_problem(d)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    net = dl.VARIANTS["v5"](m=m, n=0, d=n, batch_size=B, A=t(inp["A"]), Z0=t(inp["Z0"]),
+                            E0=t(inp["E0"]), L0=t(inp["L0"]), layers=K)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    net.cuda().requires_grad_(False)
+    X = t(inp["X"])
+    with torch.no_grad():
+        tables = net._tables(X.device)
+    W = [w.detach() for w in net._weights()]
+
+    def elz(flags, tail):
+        out = ops.ForwardResult(torch.empty((K, n, B), device="cuda"),
+                                torch.empty((K, m, B), device="cuda"),
+                                torch.empty((K, m, B), device="cuda"), None, None)
+        if tail:
+            out.P = torch.empty((K + 1, m, B), device="cuda")
+        r = ops.dladmm_forward(net.VARIANT, X, net.A, W, net.Z0, net.E0, net.L0, keep_all=True,
+                               want_T=False, out=out,
+                               flags=flags | L.F_ELZ | (L.F_ELZ_TAIL if tail else 0), **tables)
+        torch.cuda.synchronize()
+        return r
+
+    for tail in (False, True):
+        rs, fu = elz(0, tail), elz(L.F_NO_ROWSPLIT, tail)
+        assert rs.path == 5 and fu.path == 1
+        for nm in ("Z", "E", "L") + (("P",) if tail else ()):
+            a, b = getattr(rs, nm), getattr(fu, nm)
+            assert bool(torch.isfinite(b).all()), nm
+            assert torch.equal(a, b), (tail, nm, float((a - b).abs().max()))

@@ -1,7 +1,7 @@
 """V2 / V3 (per-row parameters) on the small-batch row-split forms, plan flag rowsplit_rows
-(include/dladmm.h DLADMM_F_ROWSPLIT_ROWP): forward paths 5 (csrc/dladmm_fused_rs.hip) and 6
-(csrc/dladmm_fused_xs.hip), backward paths 2 and 3 (csrc/dladmm_reverse_rs_kernel.h).  Split
-"xs" = the flag alone (path 6 where its grid fits one workgroup per CU), "rs" = the flag plus
+(include/dladmm.h DLADMM_F_ROWSPLIT_ROWP): forward paths 5 and 6
+(csrc/dladmm_fused_rs_kernel.h, MEM = 1 / 4), backward paths 2 and 3
+(csrc/dladmm_reverse_rs_kernel.h).  Split "xs" = the flag alone (path 6 where its grid fits one workgroup per CU), "rs" = the flag plus
 no_xsplit (path 5).  Without the flag V2 / V3 keep path 1 (tests/test_gpu_rowsplit.py).
 
 The forward performs the fused kernel's PK_ROW arithmetic operation for operation: every layer's

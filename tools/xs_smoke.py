@@ -1,4 +1,4 @@
-"""Quick check of path 6 (dladmm_fused_xs.hip) against path 1 at B = 20 / 300, V4 K = 6: bit
+"""Quick check of path 6 (dladmm_fused_rs_kernel.h, MEM = 4) against path 1 at B = 20 / 300, V4 K = 6: bit
 equality of every output and the wall time of each call (a hand-off that never completes shows
 up as seconds per call, never a hang: every poll is bounded)."""
 import importlib
