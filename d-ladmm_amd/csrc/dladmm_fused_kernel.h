@@ -35,6 +35,7 @@
 #include "dladmm_common.h"
 #include "dladmm_internal.h"
 #include "dladmm_ring_windows.h"
+#include "dladmm_step.h"
 
 #ifndef DLADMM_ABLATE
 #define DLADMM_ABLATE 0  // timing experiments only, see tools/ablate.py
@@ -226,27 +227,15 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
     }
   };
   // uniform per-layer scalars (s_load).  k = -1 (prologue) reads layer 0; b1n = beta1 of the
-  // layer whose Var the G2 epilogue of layer k produces (k+1, clamped).
-  struct LayerP { float b1n, b2, b3, ss2, ss2b, s1; ShrinkP the, thz; };
+  // layer whose Var the G2 epilogue of layer k produces (k+1, clamped).  The rows are chosen here
+  // as in layer_params (dladmm_step.h): calling that, the 256 x 512 kernels spill (DESIGN s. 19)
   auto layer_params = [&](int k) -> LayerP {
-    LayerP p{};
-    if constexpr (PKIND != PK_ROW) {
-      const int kk = k < 0 ? 0 : k;
-      const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
-      cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
-      // DLADMM_F_ELZ: pass G2(k) is the E / L half of step k + 1, on that row's slots
-      cfloat_p se = (cfloat_p)a.scal + (elz ? kn : kk) * DLADMM_NSCALAR;
-      p.b2 = se[DLADMM_P_BETA2];
-      // the scalar V1 form (V7) has no beta3: L = L + beta1 T, as everywhere in EM_V1
-      p.b3 = (EMODE == EM_V1 && PKIND == PK_S1) ? se[DLADMM_P_BETA1] : se[DLADMM_P_BETA3];
-      p.ss2 = se[DLADMM_P_SS2];
-      p.ss2b = se[DLADMM_P_SS2B];
-      p.the = shrink_params(se[DLADMM_P_THETA_E]);
-      p.thz = shrink_params(sp[DLADMM_P_THETA_Z]);
-      if constexpr (PKIND == PK_S1) p.s1 = sp[DLADMM_P_S1];
-      p.b1n = ((cfloat_p)a.scal)[kn * DLADMM_NSCALAR + DLADMM_P_BETA1];
-    }
-    return p;
+    const int kk = k < 0 ? 0 : k;
+    const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
+    cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
+    // DLADMM_F_ELZ: pass G2(k) is the E / L half of step k + 1, on that row's slots
+    cfloat_p se = (cfloat_p)a.scal + (elz ? kn : kk) * DLADMM_NSCALAR;
+    return layer_params_at<EMODE, PKIND>(sp, se, (cfloat_p)a.scal + kn * DLADMM_NSCALAR);
   };
   // value of param `slot` for (layer k, block b, reg r) of the per-row table
   auto rowp = [&](int k, int slot, int b, int r) -> float {
@@ -326,24 +315,15 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
   };
 #endif
   // ---------------------------------------------------------------- per-row epilogues
-  // G1 block b, row r of layer k: Z = S(Z - s1*(W_k Var), theta_z)  main_lena.py:86 / tied :114
-  // (q = -W_k Var: the chain ran on the negated packed weights, so Z + s1*q is the reference's
-  // Z - ss1*fc(Var) operation for operation; s1 = 1 outside V5)
+  // G1 block b, row r of layer k: the Z-step (z_step, dladmm_step.h) on q = -W_k Var
   auto epi1_row = [&](const LayerP& P, rsrc_t rzo, int k, int b, int r, const f32x4& q) {
 #if DLADMM_ABLATE & 2  // timing experiment: no epilogue work (WRONG results)
     Zr[b][r] = q[r]; pin_agpr(Zr[b][r]); return;
 #endif
-    const float u = (PKIND == PK_S1) ? Zr[b][r] + P.s1 * q[r] : Zr[b][r] + q[r];
-    float z;
-    if constexpr (PKIND == PK_ROW) {
-      // per-row theta in the clamp form as for the scalar kinds (common.h): for theta < 0 it
-      // gives Z = 2U exactly where both relus are open, so the backward's masks read off the
-      // saved Z_k (|Z| < 2|theta|) are exact -- the literal form can round U within an ulp of
-      // -|theta| to Z = -2|theta| and drop a term there
-      z = shrink_u(u, shrink_params(rowp(k, DLADMM_P_THETA_Z, b, r)));
-    } else {
-      z = shrink_u(u, P.thz);
-    }
+    const float z = z_step<PKIND>(Zr[b][r], q[r], P.s1, [&]() -> ShrinkP {
+      if constexpr (PKIND == PK_ROW) return shrink_params(rowp(k, DLADMM_P_THETA_Z, b, r));
+      else return P.thz;
+    });
     Zr[b][r] = z;
     pin_agpr(Zr[b][r]);
 #if DLADMM_ABLATE & 16  // timing experiment: one dwordx4 store per block, same bytes (WRONG data)
@@ -381,29 +361,18 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
       b3 = rowp(kp, DLADMM_P_BETA3, b, r);
       b1n = rowp(k + 1, DLADMM_P_BETA1, b, r);
     }
-    float e;
-    if constexpr (EMODE == EM_V1) {
-      // E = S(X - A Z - b2*L, theta_e)                      main_lena.py:87
-      const float u = (x - Pv) - b2 * l0;
-      if constexpr (PKIND == PK_ROW) e = shrink(u, rowp(kp, DLADMM_P_THETA_E, b, r));
-      else e = shrink_u(u, P.the);
-    } else if constexpr (EMODE == EM_VVAR) {
-      // VVar = L + b2*(A Z + E - X); E = S(E - ss2*VVar)    main_syn_l1l1_scalar.py:114-115
-      if constexpr (PKIND == PK_ROW) {
-        const float vv = l0 + b2 * ((Pv + e0) - x);
-        e = shrink(e0 - rowp(kp, DLADMM_P_SS2, b, r) * vv, rowp(kp, DLADMM_P_THETA_E, b, r));
-      } else {
-        const float vv = l0 + b2 * ((Pv + e0) - x);
-        e = shrink_u(e0 - P.ss2 * vv, P.the);
-      }
-    } else {
-      // E = ss2_1*(X - A Z) - ss2_2*L                       main_syn_lasso_scalar.py:102-103
-      e = P.ss2 * (x - Pv) - P.ss2b * l0;
-    }
-    e = pro ? e0 : e;
-    const float t = (Pv + e) - x;                            // main_lena.py:70 / :88
-    float l = l0 + b3 * t;                                   // main_lena.py:89 / scalar :118
-    l = pro ? l0 : l;
+    // per-row step and threshold: read where the step uses them (float: the literal shrink form)
+    const StepOut s = el_step<EMODE>(
+        Pv, x, e0, l0, b2, b3, P.ss2b, pro,
+        [&] {
+          if constexpr (PKIND == PK_ROW) return rowp(kp, DLADMM_P_SS2, b, r);
+          else return P.ss2;
+        },
+        [&] {
+          if constexpr (PKIND == PK_ROW) return rowp(kp, DLADMM_P_THETA_E, b, r);
+          else return P.the;
+        });
+    const float e = s.e, l = s.l, t = s.t;
     if constexpr (kEState) Er[b][r] = e;
     Lr[b][r] = l;
 #if DLADMM_ABLATE & 16
@@ -423,8 +392,7 @@ __global__ __launch_bounds__(256, 1) void fused_kernel(const FusedArgs a) {
     const float res = x - Pv;
     fit1 += fabsf(res);                                      // |X - A Z|
     fit2 = __builtin_fmaf(res, res, fit2);                   // (X - A Z)^2
-    // Var of the next layer: L + b1*T  (main_lena.py:85); unused after the last layer
-    Vr[b][r] = l + b1n * t;
+    Vr[b][r] = s.var(b1n);  // Var of the next layer; unused after the last layer
     if constexpr (DLADMM_VR_AGPR) pin_agpr(Vr[b][r]);
     if (r == 3) mw.next();
   };

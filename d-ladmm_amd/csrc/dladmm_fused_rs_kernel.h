@@ -32,6 +32,7 @@
 // expressions (Z the clamp form of shrink, E the literal one; tests/test_gpu_rowsplit_rowp.py).
 #pragma once
 #include "dladmm_group_xchg.h"
+#include "dladmm_step.h"
 
 #ifndef RS_PF
 #define RS_PF 4  // path 5's weight-fragment read-ahead (MFMA steps) per wave: 2, 4 and 8 time the
@@ -129,28 +130,6 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
         Lr[b][r] = bload(rl, ol + ro * (uint32_t)(a.ldl0 * 4));
       }
   }
-
-  // uniform per-layer scalars, as the fused kernel's layer_params (k = -1: the prologue)
-  struct LayerP { float b1n, b2, b3, ss2, ss2b, s1; ShrinkP the, thz; };
-  auto layer_params = [&](int k) -> LayerP {
-    LayerP p{};
-    if constexpr (kRow) return p;  // row-table operands (no scalar table)
-    const int kk = k < 0 ? 0 : k;
-    const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
-    cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
-    // DLADMM_F_ELZ: pass G2(k) is the E / L half of step k + 1, on that row's slots
-    cfloat_p se = (cfloat_p)a.scal + (elz ? kn : kk) * DLADMM_NSCALAR;
-    p.b2 = se[DLADMM_P_BETA2];
-    // the scalar V1 form (V7) has no beta3: L = L + beta1 T, as everywhere in EM_V1
-    p.b3 = (EMODE == EM_V1 && PKIND == PK_S1) ? se[DLADMM_P_BETA1] : se[DLADMM_P_BETA3];
-    p.ss2 = se[DLADMM_P_SS2];
-    p.ss2b = se[DLADMM_P_SS2B];
-    p.the = shrink_params(se[DLADMM_P_THETA_E]);
-    p.thz = shrink_params(sp[DLADMM_P_THETA_Z]);
-    if constexpr (PKIND == PK_S1) p.s1 = sp[DLADMM_P_S1];
-    p.b1n = ((cfloat_p)a.scal)[kn * DLADMM_NSCALAR + DLADMM_P_BETA1];
-    return p;
-  };
 
   float regsum = 0.f, fit1 = 0.f, fit2 = 0.f;  // this wave's rows of the layer's objective
   // V1: per-element betas of the G2 epilogue rows (b3 = beta1_k, b2 = beta2_k, b1n = beta1_k+1),
@@ -307,7 +286,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
         ca = mfma4(wa.w, vv[3], ca);
         cb = mfma4(wb.w, vv[3], cb);
       });
-      // Z = S(Z - s1*(W_k Var), theta_z): the fused kernel's epi1_row
+      // the Z-step (z_step, dladmm_step.h)
       static_for<2>([&](auto H_) {
         constexpr int h = decltype(H_)::value;
         constexpr int lb = 2 * pp + h;
@@ -315,10 +294,10 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
         f32x4 zv;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float u = (PKIND == PK_S1) ? Zr[lb][r] + P.s1 * q[r] : Zr[lb][r] + q[r];
-          float z;
-          if constexpr (kRow) z = shrink_u(u, shrink_params(tz[h][r]));  // the clamp form
-          else z = shrink_u(u, P.thz);
+          const float z = z_step<PKIND>(Zr[lb][r], q[r], P.s1, [&]() -> ShrinkP {
+            if constexpr (kRow) return shrink_params(tz[h][r]);
+            else return P.thz;
+          });
           Zr[lb][r] = z;
           zv[r] = z;
           bstore_s(rzo, vo, row_off(b1o + lb, r), X.fin(z));
@@ -385,7 +364,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
         if constexpr (HP == 2) cb2 = mfma4(wb.w, z[3], cb2);
       });
       const f32x4 qa = ca + ca2, qb = cb + cb2;
-      // the fused kernel's epi2_row
+      // el_step (dladmm_step.h); a per-row threshold (float): the literal shrink form
       static_for<HP>([&](auto H_) {
         constexpr int h = decltype(H_)::value;
         constexpr int lb = HP * pp + h;
@@ -405,25 +384,17 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
             b2 = rp[h][1][r];
             b1n = rp[h][2][r];
           }
-          float e;
-          if constexpr (EMODE == EM_V1) {
-            // E = S(X - A Z - b2*L, theta_e)                      main_lena.py:87
-            const float u = (x - Pv) - b2 * l0;
-            if constexpr (kRow) e = shrink(u, rp[h][3][r]);  // per-row theta: the literal form
-            else e = shrink_u(u, P.the);
-          } else if constexpr (EMODE == EM_VVAR) {
-            // VVar = L + b2*(A Z + E - X); E = S(E - ss2*VVar)    main_syn_l1l1_scalar.py:114-115
-            const float vv = l0 + b2 * ((Pv + e0) - x);
-            if constexpr (kRow) e = shrink(e0 - rp[h][4][r] * vv, rp[h][3][r]);
-            else e = shrink_u(e0 - P.ss2 * vv, P.the);
-          } else {
-            // E = ss2_1*(X - A Z) - ss2_2*L                       main_syn_lasso_scalar.py:102-103
-            e = P.ss2 * (x - Pv) - P.ss2b * l0;
-          }
-          e = PRO ? e0 : e;
-          const float t = (Pv + e) - x;
-          float l = l0 + b3 * t;
-          l = PRO ? l0 : l;
+          const StepOut s = el_step<EMODE>(
+              Pv, x, e0, l0, b2, b3, P.ss2b, PRO,
+              [&] {
+                if constexpr (kRow) return rp[h][4][r];
+                else return P.ss2;
+              },
+              [&] {
+                if constexpr (kRow) return rp[h][3][r];
+                else return P.the;
+              });
+          const float e = s.e, l = s.l, t = s.t;
           Er[lb][r] = e;
           Lr[lb][r] = l;
           const uint32_t so = row_off(b2o + lb, r);
@@ -434,7 +405,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
           const float res = x - Pv;
           fit1 += fabsf(res);                       // |X - A Z|
           fit2 = __builtin_fmaf(res, res, fit2);    // (X - A Z)^2
-          vv4[r] = l + b1n * t;  // Var of the next layer: L + b1*T
+          vv4[r] = s.var(b1n);  // Var of the next layer
         }
         if constexpr (MEM == 1) vx[(b2o + lb) * 64 + lane] = vv4;
         else X.xstore(rxv, b2o + lb, lane, vv4);
@@ -461,7 +432,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
     const OutR Op{elz ? mkrsrc(a.Eo, mbytes) : none, elz ? mkrsrc(a.Lo, mbytes) : none, t0,
                   elz ? mkrsrc(a.Po, a.Po ? mbytes : 0u) : none};
     if constexpr (MEM > 1) pre2();
-    g2_pass(std::true_type{}, -1, layer_params(-1), Op);
+    g2_pass(std::true_type{}, -1, layer_params<EMODE, PKIND>(a.scal, -1, K, elz), Op);
   }
   regsum = fit1 = fit2 = 0.f;  // the prologue's sums are not an objective
   X.handoff(rxv, vx, kMB, [&] {  // Var_0 complete
@@ -470,7 +441,7 @@ __global__ __launch_bounds__(256, 1) void fused_rs_kernel(const FusedArgs a) {
   for (int k = 0; k < K; ++k) {
     const bool st = a.keep_all || k == K - 1;
     const int ko = a.keep_all ? k : 0;
-    const LayerP P = layer_params(k);
+    const LayerP P = layer_params<EMODE, PKIND>(a.scal, k, K, elz);
     g1_pass(k, P, mkrsrc(a.Zo + (int64_t)ko * n * a.ldo, st ? zbytes : 0u));
     X.handoff(rxz, zx, kNB, [&] {  // Z_k complete; every wave is done reading Var_k
       if constexpr (MEM > 1) pre2();

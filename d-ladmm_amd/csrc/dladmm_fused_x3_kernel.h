@@ -45,6 +45,7 @@
 
 #include "dladmm_common.h"
 #include "dladmm_internal.h"
+#include "dladmm_step.h"
 
 #ifndef X3_ABL
 #define X3_ABL 0  // timing experiments only (tools/x3_ablate.py), every bit gives WRONG results:
@@ -447,21 +448,12 @@ __global__ __launch_bounds__(256, 1) void fused_x3_kernel(const FusedArgs a) {
   };
 
   // ---------------------------------------------------------------- parameters
-  struct LayerP { float b1n, b2, b3, ss2, ss2b, s1; ShrinkP the, thz; };
+  // the rows chosen here (never the ELZ ones): calling layer_params spills (DESIGN s. 19)
   auto layer_params = [&](int k) -> LayerP {
-    LayerP p{};
     const int kk = k < 0 ? 0 : k;
     const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
     cfloat_p sp = (cfloat_p)a.scal + kk * DLADMM_NSCALAR;
-    p.b2 = sp[DLADMM_P_BETA2];
-    p.b3 = sp[DLADMM_P_BETA3];
-    p.ss2 = sp[DLADMM_P_SS2];
-    p.ss2b = sp[DLADMM_P_SS2B];
-    p.the = shrink_params(sp[DLADMM_P_THETA_E]);
-    p.thz = shrink_params(sp[DLADMM_P_THETA_Z]);
-    if constexpr (PKIND == PK_S1) p.s1 = sp[DLADMM_P_S1];
-    p.b1n = ((cfloat_p)a.scal)[kn * DLADMM_NSCALAR + DLADMM_P_BETA1];
-    return p;
+    return dladmm::layer_params_at<EMODE, PKIND>(sp, sp, (cfloat_p)a.scal + kn * DLADMM_NSCALAR);
   };
   // weight scale exponents (pack kernel): wexp[0] = A, wexp[1 + k] = -W_k (shared: wexp[1])
   const int sw_a = __builtin_amdgcn_readfirstlane(a.wexp[0]);
@@ -540,7 +532,7 @@ __global__ __launch_bounds__(256, 1) void fused_x3_kernel(const FusedArgs a) {
     float u;
     if constexpr (PKIND == PK_S1) u = zp + acc * qs;
     else u = __builtin_fmaf(acc, qs, zp);
-    const float z = shrink_u(u, P.thz);
+    const float z = z_shrink(u, P.thz);
     zn[b & 1][r] = z;
     stage(0, r, z);
     regsum += fabsf(z);
@@ -579,19 +571,9 @@ __global__ __launch_bounds__(256, 1) void fused_x3_kernel(const FusedArgs a) {
       b2 = pb[b % 3][1][r];
       b1n = pb[b % 3][2][r];
     }
-    float e;
-    if constexpr (EMODE == EM_V1) {
-      e = shrink_u((x - Pv) - b2 * l0, P.the);                       // main_lena.py:87
-    } else if constexpr (EMODE == EM_VVAR) {
-      const float vv = l0 + P.b2 * ((Pv + e0) - x);                  // scalar :114
-      e = shrink_u(e0 - P.ss2 * vv, P.the);                          // scalar :115
-    } else {
-      e = P.ss2 * (x - Pv) - P.ss2b * l0;                            // lasso :102-103
-    }
-    e = pro ? e0 : e;
-    const float t = (Pv + e) - x;                                    // main_lena.py:88
-    float l = l0 + b3 * t;                                           // main_lena.py:89
-    l = pro ? l0 : l;
+    const StepOut s = el_step<EMODE>(Pv, x, e0, l0, b2, b3, P.ss2b, pro,
+                                     [&] { return P.ss2; }, [&] { return P.the; });
+    const float e = s.e, l = s.l, t = s.t;
     Er[b][r] = e;
     Lr[b][r] = l;
     stage(1, r, e);
@@ -600,7 +582,7 @@ __global__ __launch_bounds__(256, 1) void fused_x3_kernel(const FusedArgs a) {
     const float res = x - Pv;
     if constexpr (LQ) fit = __builtin_fmaf(res, res, fit);
     else fit += fabsf(res);
-    const float v = l + b1n * t;                                     // main_lena.py:85
+    const float v = s.var(b1n);  // Var of the next layer
     if (r & 1) vmx = amax2(vmx, vpend, v);  // rows in pairs: one v_max3
     else vpend = v;
     asm volatile("" : "+v"(fit), "+v"(vmx));

@@ -11,6 +11,7 @@
 
 #include "dladmm_common.h"
 #include "dladmm_internal.h"
+#include "dladmm_step.h"
 
 namespace dladmm {
 
@@ -108,34 +109,26 @@ struct LayerEpi {
       const int rowc = ok ? row : 0;
       const float P = accv;
       const float x = v.x, e0 = v.e0, l0 = v.l0;
-      float t, l;
-      if constexpr (PH == 2) {
-        t = (P + e0) - x;  // T0 = A Z0 + E0 - X   main_lena.py:70
-        l = l0;
-      } else {
-        float e;
-        auto pm = [&](int slot) -> float {
-          return (PKIND == PK_ROW) ? prow(rp, slot, rowc) : sp[slot];
-        };
-        if constexpr (EMODE == EM_V1) {
-          e = shrink((x - P) - v.b2 * l0, pm(DLADMM_P_THETA_E));        // main_lena.py:87
-        } else if constexpr (EMODE == EM_VVAR) {
-          const float vv = l0 + pm(DLADMM_P_BETA2) * ((P + e0) - x);     // scalar :114
-          e = shrink(e0 - pm(DLADMM_P_SS2) * vv, pm(DLADMM_P_THETA_E));  // scalar :115
-        } else {
-          e = pm(DLADMM_P_SS2) * (x - P) - pm(DLADMM_P_SS2B) * l0;        // lasso :102-103
-        }
-        t = (P + e) - x;                                                   // main_lena.py:88
-        l = l0 + v.b3 * t;                                                 // main_lena.py:89
+      // PH 2: the step's prologue form; its constant pro folds the E-step and its table reads away.
+      // float thresholds: the literal shrink form (dladmm_step.h)
+      auto pm = [&](int slot) -> float {
+        return (PKIND == PK_ROW) ? prow(rp, slot, rowc) : sp[slot];
+      };
+      const float b2 = EMODE == EM_V1 ? v.b2 : (EMODE == EM_VVAR ? pm(DLADMM_P_BETA2) : 0.f);
+      const float ss2b = EMODE == EM_LASSO ? pm(DLADMM_P_SS2B) : 0.f;
+      const StepOut s = el_step<EMODE>(P, x, e0, l0, b2, v.b3, ss2b, PH == 2,
+                                       [&] { return pm(DLADMM_P_SS2); },
+                                       [&] { return pm(DLADMM_P_THETA_E); });
+      if constexpr (PH == 1) {
         if (ok) {
-          epi_store<2>(a.Eo + (int64_t)row * a.ldo + col, e);
-          epi_store<2>(a.Lo + (int64_t)row * a.ldo + col, l);
+          epi_store<2>(a.Eo + (int64_t)row * a.ldo + col, s.e);
+          epi_store<2>(a.Lo + (int64_t)row * a.ldo + col, s.l);
         }
         const float res = x - P;
         lsum += ok ? (lasso ? res * res : fabsf(res)) : 0.0f;
       }
-      if (ok && a.To) epi_store<4>(a.To + (int64_t)row * a.ldo + col, t);
-      const float var = l + v.b1n * t;                      // Var_{k+1} = L + b1 T  main_lena.py:85
+      if (ok && a.To) epi_store<4>(a.To + (int64_t)row * a.ldo + col, s.t);
+      const float var = s.var(v.b1n);
       if (ok && a.Vo) epi_store<8>(a.Vo + (int64_t)row * a.ldv + col, var);
       return ok ? var : 0.0f;
     }

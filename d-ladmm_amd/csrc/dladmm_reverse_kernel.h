@@ -38,6 +38,7 @@
 // dispatch is dladmm_reverse.hip.
 #include "dladmm_common.h"
 #include "dladmm_internal.h"
+#include "dladmm_step.h"
 
 #ifndef REV_ABL
 #define REV_ABL 0  // timing / register-pressure experiments only (WRONG results): 1 no prologue
@@ -306,30 +307,9 @@ __global__ __launch_bounds__(256, 1) void reverse_kernel(const RevArgs a) {
     reinterpret_cast<f32x4*>(als)[(w * MB + b) * 64 + lane] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---------------------------------------------------------------- parameters
-  cfloat_p sp = (cfloat_p)a.scal;
-  // G2'(k): beta1 of BK3's layer k; BK1's layer j = k - 1 (the prologue: j = K - 1)
-  struct LP2 { float b1k, b1, b2, b3, ss2, ss2b, the, cf; };
-  auto lp2 = [&](int k, int jl) -> LP2 {
-    LP2 p{};
-    const int kk = k < K ? k : K - 1;
-    const int jj = jl < 0 ? 0 : jl;
-    p.cf = a.loss_kind ? ((cfloat_p)a.lcoef)[2 * jj + 1] : 0.f;
-    if constexpr (ROWP) return p;  // per-row parameters: row-table operands (no scalar table)
-    p.b1k = sp[kk * DLADMM_NSCALAR + DLADMM_P_BETA1];
-    p.b1 = sp[jj * DLADMM_NSCALAR + DLADMM_P_BETA1];
-    p.b2 = sp[jj * DLADMM_NSCALAR + DLADMM_P_BETA2];
-    p.b3 = sp[jj * DLADMM_NSCALAR + DLADMM_P_BETA3];
-    p.ss2 = sp[jj * DLADMM_NSCALAR + DLADMM_P_SS2];
-    p.ss2b = sp[jj * DLADMM_NSCALAR + DLADMM_P_SS2B];
-    p.the = sp[jj * DLADMM_NSCALAR + DLADMM_P_THETA_E];
-    return p;
-  };
-  // G1'(k): the mask bound c from theta_z (0 for theta_z >= 0, else 2|theta_z|) and cz_k
-  struct LP1 { float c, cz; };
-  auto lp1 = [&](int k) -> LP1 {
-    const float th = ROWP ? 0.f : sp[k * DLADMM_NSCALAR + DLADMM_P_THETA_Z];
-    return LP1{th >= 0.f ? 0.f : -2.0f * th, a.loss_kind ? ((cfloat_p)a.lcoef)[2 * k] : 0.f};
-  };
+  // G2'(k) / G1'(k) scalars: load_lp2 / load_lp1 (dladmm_step.h)
+  auto lp2 = [&](int k, int jl) { return load_lp2<ROWP>(a.scal, a.lcoef, a.loss_kind, k, jl, K); };
+  auto lp1 = [&](int k) { return load_lp1<ROWP>(a.scal, a.lcoef, a.loss_kind, k); };
 
   // ---------------------------------------------------------------- operand views
   // BK1 of layer j reads P_j, E_{j-1}, L_{j-1} (E0 / L0 for j = 0, their own strides), T_j;
@@ -560,23 +540,14 @@ __global__ __launch_bounds__(256, 1) void reverse_kernel(const RevArgs a) {
     if constexpr (REV_ABL & 4) { AZ[b][r] = q[r]; pin_agpr(AZ[b][r]); return; }
     const int st = set1(b / 2);
     const float zk = pz[st][h][r];
-    float cth = P1.c;
+    const float cth = ROWP ? z_mask_bound(pt[st][h][r]) : P1.c;
+    // BK2 (z_adjoint, dladmm_step.h) on the complete adjoint of Z_k
+    const ZAdj za = z_adjoint((GZ ? AZ[b][r] + pg[st][h][r] : AZ[b][r]) + q[r], zk, cth, P1.cz);
+    const float gU = za.gU;
     if constexpr (ROWP) {
-      const float th = pt[st][h][r];
-      cth = th >= 0.f ? 0.f : -2.0f * th;
-    }
-    float gZt = (GZ ? AZ[b][r] + pg[st][h][r] : AZ[b][r]) + q[r];
-    // + d/dZ_k of cz_k sum|Z_k|: cz_k sgn(Z_k) is exact, so the fma is phase 5's mul + add
-    const float sg = (zk > 0.f ? 1.f : 0.f) - (zk < 0.f ? 1.f : 0.f);
-    gZt = __builtin_fmaf(P1.cz, sg, gZt);
-    // S'(U) = [U - th > 0] + [-U - th > 0] in {0, 1, 2}, from Z_k = S(U, th); gZt * S' as a
-    // sum of selected gZt (exact), d/dth = [-U - th > 0] - [U - th > 0]
-    const float ga = zk > -cth ? gZt : 0.f, gb = zk < cth ? gZt : 0.f;
-    const float gU = ga + gb;
-    if constexpr (ROWP) {
-      pstore(rzk.pk, pso(DLADMM_P_THETA_Z) + wP1.at(r), 16 * b + 4 * g + r, a.n, gb - ga);
+      pstore(rzk.pk, pso(DLADMM_P_THETA_Z) + wP1.at(r), 16 * b + 4 * g + r, a.n, za.pth);
     } else {
-      psz += gb - ga;
+      psz += za.pth;
       asm volatile("" : "+v"(psz));
     }
     AZ[b][r] = gU;  // adjoint of Z_{k-1}
@@ -653,65 +624,13 @@ __global__ __launch_bounds__(256, 1) void reverse_kernel(const RevArgs a) {
       const float aE = COT ? aE0 + pvs(S_GE_t{}, 0.f) : aE0;
       const float Pv = pv[r][S_P], lp = pv[r][S_L], x = pv[r][S_X];
       const float b1 = pvs(S_B1J_t{}, P.b1);
-      float gP, gEp = 0.f, gLp, t;
+      // BK1 of layer k - 1 (el_adjoint, dladmm_step.h)
+      const float ep = pvs(std::integral_constant<int, kAE ? S_E : NS>{}, 0.f);
+      const ElAdj ad = el_adjoint<EMODE, ROWP>(aL, aT, aE, Pv, lp, ep, x, b1, b2p, b3p, ss2p, P.ss2b,
+                                               thep, P.cf, lqm);
+      const float gP = ad.gP, gEp = ad.gEp, gLp = ad.gLp, t = ad.t;
+      const float p3 = ad.p3, p2 = ad.p2, pe = ad.pe, ps2 = ad.ps2, ps2b = ad.ps2b;
       (void)gEp;
-      float p3 = 0.f, p2 = 0.f, pe = 0.f, ps2 = 0.f, ps2b = 0.f;
-      if constexpr (EMODE == EM_V1) {
-        const float b2 = b2p;
-        const float u = (x - Pv) - b2 * lp;               // main_lena.py:87
-        // E_{k-1} as the forward formed it (scalar theta: the clamp form; common.h)
-        const float e = ROWP ? shrink(u, thep) : shrink_u(u, shrink_params(thep));
-        t = (Pv + e) - x;                                 // T_k
-        const float gTn = aT + b1 * aL;                   // L_{k-1} = L_{k-2} + b1 T_k (:89)
-        p3 = aL * t;
-        const float gEt = aE + gTn;
-        const float ga = (u - thep) > 0.0f ? gEt : 0.f;
-        const float gb = (-u - thep) > 0.0f ? gEt : 0.f;
-        const float gEh = ga + gb;
-        pe = gb - ga;                                     // V2's per-row theta_e
-        gP = gTn - gEh;
-        p2 = -gEh * lp;
-        gLp = aL - b2 * gEh;
-      } else if constexpr (EMODE == EM_VVAR) {
-        const float ep = pv[r][S_E];
-        const float r0 = (Pv + ep) - x;
-        const float vv = lp + b2p * r0;                   // main_syn_l1l1_scalar.py:114
-        const float eh = ep - ss2p * vv;                  // :115
-        const float e = ROWP ? shrink(eh, thep) : shrink_u(eh, shrink_params(thep));
-        t = (Pv + e) - x;                                 // T_k
-        const float gTn = aT + b3p * aL;
-        p3 = aL * t;
-        const float gEt = aE + gTn;
-        // shrink' = [eh - th > 0] + [-eh - th > 0]: gEt times it as a sum of selected gEt
-        const float ga = (eh - thep) > 0.0f ? gEt : 0.f;
-        const float gb = (-eh - thep) > 0.0f ? gEt : 0.f;
-        const float gEh = ga + gb;
-        pe = gb - ga;
-        const float gVV = -ss2p * gEh;
-        ps2 = -gEh * vv;
-        gLp = aL + gVV;
-        p2 = gVV * r0;
-        gP = gTn + b2p * gVV;
-        gEp = gEh + b2p * gVV;
-      } else {
-        const float e = P.ss2 * (x - Pv) - P.ss2b * lp;   // main_syn_lasso_scalar.py:102-103
-        t = (Pv + e) - x;
-        const float gTn = aT + P.b3 * aL;
-        p3 = aL * t;
-        const float gEt = aE + gTn;
-        ps2 = gEt * (x - Pv);
-        gP = gTn - P.ss2 * gEt;
-        ps2b = -gEt * lp;
-        gLp = aL - P.ss2b * gEt;
-      }
-      {  // d/dP of cf * fit (fit = sum|X - P|, torch sgn(0) = 0, or 0.5 sum (X - P)^2)
-        const float res = x - Pv;
-        const float sg = (res > 0.f ? 1.f : 0.f) - (res < 0.f ? 1.f : 0.f);
-        // uniform select by bit mask (a per-row branch here splits the unrolled body)
-        const float dfit = __builtin_bit_cast(
-            float, (lqm & __builtin_bit_cast(uint32_t, res)) | (~lqm & __builtin_bit_cast(uint32_t, sg)));
-        gP = gP - P.cf * dfit;
-      }
       if constexpr (kV1) {
         // beta1_k's gradient = BK1(k)'s term + gVar T_k (the per-layer order); beta1_{k-1} gets
         // BK1(k-1)'s term aL T_k now and BK3(k-1)'s next pass; beta2_{k-1} complete
@@ -741,13 +660,8 @@ __global__ __launch_bounds__(256, 1) void reverse_kernel(const RevArgs a) {
       GP[b][r] = gP;
       pin_agpr(GP[b][r]);
       als[al_at(b, r)] = gLp;
-      // Var of layer k (BK3's): L_{k-1} + beta1_k T_k from the values just recomputed, the
-      // forward's own expression (l = L_{k-2} + c T_k, then + beta1_k T_k; c = the L-update
-      // coefficient), so T_{k-1} is never loaded.  The prologue's (layer K) is dropped: its
-      // store runs past rv's last layer block.
-      const float lcoef = EMODE == EM_V1 ? b1 : (EMODE == EM_VVAR ? b3p : P.b3);
-      const float lk = lp + lcoef * t;
-      const float vark = lk + b1k * t;
+      // Var of layer k (BK3's), var_k; the prologue's (layer K) runs past rv's last block: dropped
+      const float vark = var_k<EMODE>(lp, t, b1, b3p, b1k);
       if constexpr (!(REV_ABL & 64)) {
         bstore_s(rv, vw, vas4 + wV.at(r), vark);
         if constexpr (kAE) bstore_s((REV_ABL & 128) ? none : rv, vw, wV.at(r) + aeo, gEp);  // adjoint of E_{k-2}

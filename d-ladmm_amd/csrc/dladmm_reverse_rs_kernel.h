@@ -27,6 +27,7 @@
 // dladmm_reverse_rs_v2.hip / _v3.hip (one translation unit each: the build stays parallel).
 #pragma once
 #include "dladmm_group_xchg.h"
+#include "dladmm_step.h"
 
 #ifndef RRS_PF
 #define RRS_PF 4  // weight-fragment read-ahead (MFMA steps) per wave
@@ -141,28 +142,9 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
     for (int i = 0; i < 5; ++i) ps[i] = 0.f;
   };
 
-  // parameters (the reverse sweep's lp2 / lp1)
-  cfloat_p sp = (cfloat_p)a.scal;
-  struct LP2 { float b1k, b2, b3, ss2, ss2b, the, cf; };
-  auto lp2 = [&](int k, int jl) -> LP2 {
-    LP2 p{};
-    const int kk = k < K ? k : K - 1;
-    const int jj = jl < 0 ? 0 : jl;
-    p.cf = a.loss_kind ? ((cfloat_p)a.lcoef)[2 * jj + 1] : 0.f;
-    if constexpr (ROWP) return p;  // per-row parameters: row-table operands (no scalar table)
-    p.b1k = sp[kk * DLADMM_NSCALAR + DLADMM_P_BETA1];
-    p.b2 = sp[jj * DLADMM_NSCALAR + DLADMM_P_BETA2];
-    p.b3 = sp[jj * DLADMM_NSCALAR + DLADMM_P_BETA3];
-    p.ss2 = sp[jj * DLADMM_NSCALAR + DLADMM_P_SS2];
-    p.ss2b = sp[jj * DLADMM_NSCALAR + DLADMM_P_SS2B];
-    p.the = sp[jj * DLADMM_NSCALAR + DLADMM_P_THETA_E];
-    return p;
-  };
-  struct LP1 { float c, cz; };
-  auto lp1 = [&](int k) -> LP1 {
-    const float th = ROWP ? 0.f : sp[k * DLADMM_NSCALAR + DLADMM_P_THETA_Z];
-    return LP1{th >= 0.f ? 0.f : -2.0f * th, a.loss_kind ? ((cfloat_p)a.lcoef)[2 * k] : 0.f};
-  };
+  // G2'(k) / G1'(k) scalars: load_lp2 / load_lp1 (dladmm_step.h)
+  auto lp2 = [&](int k, int jl) { return load_lp2<ROWP>(a.scal, a.lcoef, a.loss_kind, k, jl, K); };
+  auto lp1 = [&](int k) { return load_lp1<ROWP>(a.scal, a.lcoef, a.loss_kind, k); };
 
   // ROWP (the reverse sweep's row-table operands and per-row partials): the row table
   // [K][8][rstride] (lane: rows 4 g .. of a block, the 16 lanes of a row on one address; rows past
@@ -253,18 +235,13 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float zk = pz[lb][r];
-          float cth = P1.c;
-          if constexpr (ROWP) {  // theta_z's mask bound is per row
-            const float th = pt[ROWP ? lb : 0][r];
-            cth = th >= 0.f ? 0.f : -2.0f * th;
-          }
-          float gZt = (GZ ? AZ[lb][r] + pg[GZ ? lb : 0][r] : AZ[lb][r]) + q[r];
-          const float sg = (zk > 0.f ? 1.f : 0.f) - (zk < 0.f ? 1.f : 0.f);
-          gZt = __builtin_fmaf(P1.cz, sg, gZt);
-          const float ga = zk > -cth ? gZt : 0.f, gb = zk < cth ? gZt : 0.f;
-          const float gU = ga + gb;
-          if constexpr (ROWP) pstore(rpk1, DLADMM_P_THETA_Z, b1o + lb, r, gb - ga);
-          else psz += gb - ga;
+          // BK2 (z_adjoint, dladmm_step.h); theta_z's mask bound is per row under ROWP
+          const float cth = ROWP ? z_mask_bound(pt[ROWP ? lb : 0][r]) : P1.c;
+          const ZAdj za = z_adjoint(
+              (GZ ? AZ[lb][r] + pg[GZ ? lb : 0][r] : AZ[lb][r]) + q[r], zk, cth, P1.cz);
+          const float gU = za.gU;
+          if constexpr (ROWP) pstore(rpk1, DLADMM_P_THETA_Z, b1o + lb, r, za.pth);
+          else psz += za.pth;
           AZ[lb][r] = gU;
           gu4[r] = X.fin(gU);
           bstore_s(rg, vw, row_off(b1o + lb, r, ldw4), gu4[r]);
@@ -436,7 +413,7 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
         qa4[0] = ca;
         qa4[1] = cb;
       }
-      // epilogue rows (the reverse sweep's epi2_row)
+      // epilogue rows: BK3 / BK1 as in the 64-column sweep (el_adjoint, dladmm_step.h)
 #pragma unroll
     for (int h = 0; h < HP; ++h) {
       const int lb = HP * pp + h;
@@ -474,63 +451,14 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
         const float b3p = (ROWP && kAE) ? op[h][O_RB3J][r] : P.b3;
         const float ss2p = (ROWP && kAE) ? op[h][O_RSS2][r] : P.ss2;
         const float thep = ROWP ? op[h][O_RTHE][r] : P.the;
-        float gP, gEp = 0.f, gLp, t;
+        // BK1 of layer j (el_adjoint, dladmm_step.h); V1's beta2 is per sample
+        const float b2 = (EMODE == EM_V1 && !ROWP) ? op[h][O_B2J][r] : b2p;
+        const float ep = kAE ? op[h][O_E][r] : 0.f;
+        const ElAdj ad = el_adjoint<EMODE, ROWP>(aL, aT, aE, Pv, lp, ep, x, b1, b2, b3p, ss2p,
+                                                 P.ss2b, thep, P.cf, lqm);
+        const float gP = ad.gP, gEp = ad.gEp, gLp = ad.gLp, t = ad.t;
+        const float p3 = ad.p3, p2 = ad.p2, pe = ad.pe, ps2 = ad.ps2, ps2b = ad.ps2b;
         (void)gEp;
-        float p3 = 0.f, p2 = 0.f, pe = 0.f, ps2 = 0.f, ps2b = 0.f;
-        if constexpr (EMODE == EM_V1) {
-          const float b2 = ROWP ? b2p : op[h][O_B2J][r];
-          const float u = (x - Pv) - b2 * lp;               // main_lena.py:87
-          // E_{k-1} as the forward formed it (scalar theta: the clamp form; per-row: the literal)
-          const float e = ROWP ? shrink(u, thep) : shrink_u(u, shrink_params(thep));
-          t = (Pv + e) - x;                                 // T_k
-          const float gTn = aT + b1 * aL;                   // L_{k-1} = L_{k-2} + b1 T_k (:89)
-          p3 = aL * t;
-          const float gEt = aE + gTn;
-          const float ga = (u - thep) > 0.0f ? gEt : 0.f;
-          const float gb = (-u - thep) > 0.0f ? gEt : 0.f;
-          const float gEh = ga + gb;
-          pe = gb - ga;
-          gP = gTn - gEh;
-          p2 = -gEh * lp;
-          gLp = aL - b2 * gEh;
-        } else if constexpr (EMODE == EM_VVAR) {
-          const float ep = op[h][O_E][r];
-          const float r0 = (Pv + ep) - x;
-          const float vv = lp + b2p * r0;                   // main_syn_l1l1_scalar.py:114
-          const float eh = ep - ss2p * vv;                  // :115
-          const float e = ROWP ? shrink(eh, thep) : shrink_u(eh, shrink_params(thep));
-          t = (Pv + e) - x;                                 // T_k
-          const float gTn = aT + b3p * aL;
-          p3 = aL * t;
-          const float gEt = aE + gTn;
-          const float ga = (eh - thep) > 0.0f ? gEt : 0.f;
-          const float gb = (-eh - thep) > 0.0f ? gEt : 0.f;
-          const float gEh = ga + gb;
-          pe = gb - ga;
-          const float gVV = -ss2p * gEh;
-          ps2 = -gEh * vv;
-          gLp = aL + gVV;
-          p2 = gVV * r0;
-          gP = gTn + b2p * gVV;
-          gEp = gEh + b2p * gVV;
-        } else {
-          const float e = P.ss2 * (x - Pv) - P.ss2b * lp;  // main_syn_lasso_scalar.py:102-103
-          t = (Pv + e) - x;
-          const float gTn = aT + P.b3 * aL;
-          p3 = aL * t;
-          const float gEt = aE + gTn;
-          ps2 = gEt * (x - Pv);
-          gP = gTn - P.ss2 * gEt;
-          ps2b = -gEt * lp;
-          gLp = aL - P.ss2b * gEt;
-        }
-        {  // d/dP of cf * fit (fit = sum|X - P|, torch sgn(0) = 0, or 0.5 sum (X - P)^2)
-          const float res = x - Pv;
-          const float sg = (res > 0.f ? 1.f : 0.f) - (res < 0.f ? 1.f : 0.f);
-          const float dfit = __builtin_bit_cast(
-              float, (lqm & __builtin_bit_cast(uint32_t, res)) | (~lqm & __builtin_bit_cast(uint32_t, sg)));
-          gP = gP - P.cf * dfit;
-        }
         if constexpr (kV1) {
           // beta1_k's gradient = BK1(k)'s term + gVar T_k; beta1_{k-1} gets BK1(k-1)'s term
           // aL T_k now and BK3(k-1)'s next pass; beta2_{k-1} complete
@@ -553,9 +481,7 @@ __global__ __launch_bounds__(256, 1) void reverse_rs_kernel(const RevArgs a) {
         AL[lb][r] = gLp;
         // Var of layer k: L_{k-1} + beta1_k T_k from the recomputed values (the prologue's,
         // layer K, runs past the workspace: dropped)
-        const float lcoef = EMODE == EM_V1 ? b1 : b3p;
-        const float lk = lp + lcoef * t;
-        const float vark = lk + b1k * t;
+        const float vark = var_k<EMODE>(lp, t, b1, b3p, b1k);
         bstore_s(rv, vw, vas4 + sw, vark);
         if constexpr (kAE) bstore_s(rv, vw, sw + aeo, gEp);  // adjoint of E_{k-2}
       }

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--layers", type=int, default=15)
-    ap.add_argument("--variant", default="v4", choices=["v2", "v3", "v4"],
+    ap.add_argument("--variant", default="v4", choices=["v1", "v2", "v3", "v4"],
                     help="model variant; v2 / v3 (per-row parameters) reach bwd paths 3 / 2 with "
                          "the forward plan flag rowsplit_rows (256), e.g. --flag-set 256,384,0")
     ap.add_argument("--gz", action="store_true",
