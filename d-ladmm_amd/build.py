@@ -24,6 +24,8 @@ UNITS = ("dladmm_capi.hip", "dladmm_fused.hip", "dladmm_fused_savep.hip",
          "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip", "dladmm_fused_x3.hip",
          "dladmm_fused_x3_savep.hip", "dladmm_fused_rs.hip", "dladmm_fused_xs.hip",
          "dladmm_layered.hip", "dladmm_backward.hip", "dladmm_lskm.hip", "dladmm_eval.hip",
+         # the safeguarded LSKM forward as one launch
+         "dladmm_lskm_fused.hip",
          "dladmm_tile_bf16.hip", "dladmm_wgrad_x3.hip",
          "dladmm_reverse.hip", "dladmm_reverse_rs.hip",
          "dladmm_lena.hip",
@@ -48,13 +50,17 @@ UNIT_FLAGS = {u: ["-fno-slp-vectorize"] for u in UNITS
 # the split-f16 weight gradient unscales every MFMA result with VALU: MFMA results in VGPRs
 # (no v_accvgpr_read per element)
 UNIT_FLAGS["dladmm_wgrad_x3.hip"] = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+# no packed f32 VALU (v_pk_*_f32) in the one-launch LSKM kernel's epilogues
+UNIT_FLAGS["dladmm_lskm_fused.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # The fused fp32 kernel keeps its whole state in registers; which instantiations take the two-slot
 # weight ring (csrc/dladmm_fused_kernel.h kRing2) rests on a register census.
 # So these units are compiled with the resource-usage remarks, and a kernel of theirs whose
 # scratch exceeds what is recorded here (bytes per lane, by the kernel's mangled template
 # arguments <MP, NP, EMODE, PKIND, SAVEP, P0LOAD, ELZ>; every other kernel: 0) fails the build.
 CENSUS_UNITS = ("dladmm_fused.hip", "dladmm_fused_savep.hip", "dladmm_fused_elz.hip",
-                "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip")
+                "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip",
+                # lskm_fused_kernel holds three states per lane: no scratch, ever
+                "dladmm_lskm_fused.hip")
 SCRATCH_RECORD = {
     "ILi256ELi512ELi1ELi0ELb1ELb0ELb1E": 416,   # V4, ELZ unit
     "ILi256ELi512ELi1ELi3ELb1ELb0ELb1E": 416,   # V5, ELZ unit

@@ -9,6 +9,7 @@
 #include "dladmm_common.h"
 #include "dladmm_wgrad_x3.h"
 #include "dladmm_internal.h"
+#include "dladmm_lskm_fused.h"
 
 namespace dladmm {
 
@@ -1495,9 +1496,86 @@ inline int lena_plan(const dladmm_lena_desc* d, LenaPlan* p) {
   return 0;
 }
 
+// ---- the safeguarded LSKM forward as one launch (dladmm_lskm_fused.hip)
+// workspace: packed A, packed -A^T, packed -W_0 .. -W_{layers-1}
+inline int lskm_validate(const dladmm_lskm_desc* d) {
+  if (!d) return DLADMM_E_NULL;
+  if (d->abi_version != DLADMM_ABI_VERSION) return DLADMM_E_ABI_VERSION;
+  if (d->m < 1 || d->n < 1 || d->batch < 1) return DLADMM_E_SHAPE;
+  if (d->layers < 1 || d->layers > DLADMM_MAX_LAYERS) return DLADMM_E_LAYERS;
+  if (d->m > kShapeMP[2] || d->n > kShapeNP[2]) return DLADMM_E_UNSUPPORTED;
+  if (d->updater < DLADMM_MU_NONE || d->updater > DLADMM_MU_RT) return DLADMM_E_UNSUPPORTED;
+  const void* req[] = {d->X, d->A, d->Z0, d->E0, d->L0, d->W, d->scalar_params, d->km_params,
+                       d->Z, d->E, d->L, d->T, d->count, d->workspace};
+  for (const void* p : req)
+    if (!p) return DLADMM_E_NULL;
+  for (int k = 0; k < d->layers; ++k)
+    if (!d->W[k]) return DLADMM_E_NULL;
+  const int64_t B = d->batch;
+  if (d->ld_x < B || d->ld_z0 < B || d->ld_e0 < B || d->ld_l0 < B || d->ld_out < B ||
+      d->ld_a < d->n || d->ld_w < d->m)
+    return DLADMM_E_SHAPE;
+  // 32-bit buffer offsets over the instantiation's padded rows (a lane outside the batch starts
+  // at kOOB = 2^31 plus the row offset, which must stay out of range: lena_plan)
+  const int64_t lim = (int64_t)1 << 31, NPs = kShapeNP[2];
+  if (NPs * d->ld_x * 4 >= lim || NPs * d->ld_z0 * 4 >= lim || NPs * d->ld_e0 * 4 >= lim ||
+      NPs * d->ld_l0 * 4 >= lim || NPs * d->ld_out * 4 >= lim)
+    return DLADMM_E_UNSUPPORTED;
+  return 0;
+}
+inline size_t lskm_bytes(const dladmm_lskm_desc* d) {
+  return align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float)) * (size_t)(2 + d->layers);
+}
+
 }  // namespace dladmm
 
 extern "C" {
+
+size_t dladmm_lskm_workspace_bytes(const dladmm_lskm_desc* d) {
+  using namespace dladmm;
+  // sizing needs the shape alone: the workspace pointer is what the caller is about to allocate
+  if (!d || d->abi_version != DLADMM_ABI_VERSION || d->layers < 1 ||
+      d->layers > DLADMM_MAX_LAYERS || d->m < 1 || d->n < 1 || d->m > kShapeMP[2] ||
+      d->n > kShapeNP[2])
+    return 0;
+  return lskm_bytes(d);
+}
+
+int dladmm_lskm_f32(const dladmm_lskm_desc* d, void* stream) {
+  using namespace dladmm;
+  if (int e = lskm_validate(d)) return e;
+  const size_t fb = align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float));
+  if (d->workspace_bytes < lskm_bytes(d)) return DLADMM_E_WORKSPACE;
+  if (((uintptr_t)d->workspace) & 255) return DLADMM_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)d->workspace;
+  float* Ap = (float*)ws;
+  float* Atp = (float*)(ws + fb);
+  float* Wp = (float*)(ws + 2 * fb);
+  const int MB = kShapeMP[2] / 16, NB = kShapeNP[2] / 16;
+  // every weight once per call: -W_k, A, and -A^T (the KM step's weight, the transposed read of A:
+  // the same values a pack of the contiguous A^T writes)
+  if (hipError_t e = pack(d->W, d->layers, d->n, d->m, d->ld_w, NB, MB, 2, Wp, s, -1.0f))
+    return (int)e;
+  const float* asrc[1] = {d->A};
+  if (hipError_t e = pack(asrc, 1, d->m, d->n, d->ld_a, MB, NB, 2, Ap, s)) return (int)e;
+  if (hipError_t e = pack(asrc, 1, d->n, d->m, d->ld_a, NB, MB, 2, Atp, s, -1.0f, nullptr, 1))
+    return (int)e;
+  if (hipError_t e = zero_async(d->count, (size_t)d->layers * sizeof(int32_t), s)) return (int)e;
+  LskmArgs a{};
+  a.m = d->m; a.n = d->n; a.B = d->batch; a.K = d->layers;
+  a.X = d->X; a.ldx = d->ld_x;
+  a.Z0 = d->Z0; a.ldz0 = d->ld_z0;
+  a.E0 = d->E0; a.lde0 = d->ld_e0;
+  a.L0 = d->L0; a.ldl0 = d->ld_l0;
+  a.Ap = Ap; a.Atp = Atp; a.Wp = Wp;
+  a.scal = d->scalar_params; a.km = d->km_params;
+  a.Zo = d->Z; a.Eo = d->E; a.Lo = d->L; a.To = d->T; a.ldo = d->ld_out;
+  a.count = d->count; a.mu_out = d->mu_out;
+  a.beta = d->beta; a.c = d->c; a.thresh = (float)(1.0 - d->delta);  // python (1.0-delta)
+  a.param = d->mu_param; a.updater = d->updater;
+  return (int)launch_lskm_fused(a, ceil_div(d->batch, 16), s);
+}
 
 size_t dladmm_lena_workspace_bytes(const dladmm_lena_desc* d) {
   using namespace dladmm;

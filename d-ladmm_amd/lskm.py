@@ -13,7 +13,9 @@ Every step runs on the HIP kernels:
     truth of the test scripts) is ONE kernel launch with the weight packed once;
   * a learned step is the V4 path on layer k's parameters;
   * the safeguard (fixed-point residual norm, mu update, per-column select) is
-    `dladmm_safeguard_f32` (csrc/dladmm_lskm.hip).
+    `dladmm_safeguard_f32` (csrc/dladmm_lskm.hip);
+  * at the 256 x 512 register shape the whole learned + safeguarded loop is ONE kernel launch,
+    `dladmm_lskm_f32` (csrc/dladmm_lskm_fused.hip; `fused_safeguard`), with the same outputs.
 """
 from __future__ import annotations
 
@@ -26,7 +28,7 @@ import torch
 
 from . import _lib
 from .model import DLADMMNetScalar, _scalar_table
-from .ops import dladmm_forward
+from .ops import _f32_dev, _workspace, dladmm_forward
 
 _UPDATERS = {"None": _lib.MU_NONE, "EMA": _lib.MU_EMA, "GS": _lib.MU_GS, "RT": _lib.MU_RT}
 
@@ -40,8 +42,11 @@ class DLADMMNetLSKM(DLADMMNetScalar):
 
     def __init__(self, m, n, d, batch_size, A, Z0, E0, L0, layers, *, alpha: float = 0.01,
                  delta: float = -99.0, mu_k_method: str = "None", mu_k_param: float = 0.0,
-                 num_iter: int = 200):
+                 num_iter: int = 200, fused_safeguard: Optional[bool] = None):
         super().__init__(m, n, d, batch_size, A, Z0, E0, L0, layers)
+        # the learned + safeguarded loop as one launch (dladmm_lskm_f32): True requires it, False
+        # keeps the per-layer launches, None takes it wherever the kernel exists (_fused_shape)
+        self.fused_safeguard = fused_safeguard
         if mu_k_method == "RM":
             raise NotImplementedError(
                 "mu_k_method 'RM': the reference RMUpdater.step returns torch's (values, indices) "
@@ -128,10 +133,58 @@ class DLADMMNetLSKM(DLADMMNetScalar):
         stream = torch.cuda.current_stream(x.device).cuda_stream
         _lib.check(L.dladmm_safeguard_f32(ctypes.byref(d), ctypes.c_void_p(stream)))
 
+    def _fused_shape(self) -> bool:
+        """The fused forward's 256 x 512 instantiation (pick_shape, csrc/dladmm_capi.hip): the one
+        shape dladmm_lskm_f32 is built for."""
+        m, n = self.A.shape
+        return m <= 256 and n <= 512 and not (m <= 64 and n <= 256)
+
+    def _lskm_fused(self, x, nl: int, Zo, Eo, Lo, To, count):
+        """dladmm_lskm_f32: layers 0 .. nl-1 of the safeguarded loop, one kernel launch."""
+        Lb = _lib.lib()
+        dev = x.device
+        X, A = _f32_dev(x, "X"), _f32_dev(self.A, "A")
+        Z0, E0, L0 = _f32_dev(self.Z0, "Z0"), _f32_dev(self.E0, "E0"), _f32_dev(self.L0, "L0")
+        m, B = X.shape
+        n = A.shape[1]
+        if A.shape[0] != m or tuple(Z0.shape) != (n, B) or tuple(E0.shape) != (m, B) or \
+                tuple(L0.shape) != (m, B):
+            raise RuntimeError("dladmm: Z0/E0/L0 shapes do not broadcast with X")
+        Ws = [_f32_dev(self.fc[k].weight.detach().contiguous(), f"W[{k}]") for k in range(nl)]
+        ptab = self._tables(dev)["scalar_params"][:nl].contiguous()
+        km = self._km_table(1)
+        warr = _lib.ptr_array([w.data_ptr() for w in Ws])
+        d = _lib.LskmDesc()
+        d.abi_version = _lib.ABI_VERSION
+        d.m, d.n, d.batch, d.layers = m, n, B, nl
+        d.X, d.ld_x = X.data_ptr(), X.stride(0)
+        d.A, d.ld_a = A.data_ptr(), A.stride(0)
+        d.Z0, d.ld_z0 = Z0.data_ptr(), Z0.stride(0)
+        d.E0, d.ld_e0 = E0.data_ptr(), E0.stride(0)
+        d.L0, d.ld_l0 = L0.data_ptr(), L0.stride(0)
+        d.W, d.ld_w = ctypes.cast(warr, ctypes.POINTER(ctypes.c_void_p)), m
+        d.scalar_params, d.km_params = ptab.data_ptr(), km.data_ptr()
+        d.beta, d.c, d.delta = 1.0, sqrt(0.3 / (1 - 0.3)), self.delta
+        d.updater, d.mu_param = _UPDATERS[self.mu_k_method], self.mu_k_param
+        d.Z, d.E, d.L, d.T, d.ld_out = Zo.data_ptr(), Eo.data_ptr(), Lo.data_ptr(), \
+            To.data_ptr(), B
+        d.count = count.data_ptr()
+        wsb = Lb.dladmm_lskm_workspace_bytes(ctypes.byref(d))
+        ws = _workspace(dev, max(wsb, 1))
+        d.workspace, d.workspace_bytes = ws.data_ptr(), wsb
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(Lb.dladmm_lskm_f32(ctypes.byref(d), ctypes.c_void_p(stream)))
+
     def forward(self, x, use_learned=False, use_safeguard=False, continued=False,
-                K: Optional[int] = None):
+                K: Optional[int] = None, fused_safeguard: Optional[bool] = None):
         """test_syn_l1l1_scalar.py:178-316.  K defaults to the reference's
-        `layers if (not continued and (use_learned or use_safeguard)) else num_iter` (:54)."""
+        `layers if (not continued and (use_learned or use_safeguard)) else num_iter` (:54).
+        fused_safeguard overrides the constructor's setting for this call."""
+        fused = self.fused_safeguard if fused_safeguard is None else fused_safeguard
+        if fused and (self.A.shape[0] > 256 or self.A.shape[1] > 512):
+            raise ValueError(
+                f"dladmm: fused_safeguard=True needs the 256 x 512 register shape (m <= 256, "
+                f"n <= 512), got m={self.A.shape[0]}, n={self.A.shape[1]}")
         if K is None:
             K = self.layers if (not continued and (use_learned or use_safeguard)) else \
                 self.num_iter
@@ -153,6 +206,12 @@ class DLADMMNetLSKM(DLADMMNetScalar):
                 Lo = torch.empty((nl, m, B), device=dev)
                 To = torch.empty((nl + 1, m, B), device=dev)
                 count = torch.zeros(self.layers, dtype=torch.int32, device=dev)
+                if fused is None:
+                    fused = self._fused_shape()
+            if use_safeguard and fused and nl > 0 and B > 0:
+                self._lskm_fused(x, nl, Zo, Eo, Lo, To, count)
+                Z, E, L, T = list(Zo), list(Eo), list(Lo), list(To)
+            elif use_safeguard:
                 mu = torch.empty(B, device=dev)
                 # mu_0 = |S(Z0, E0, L0, T0, X, E0)| (:190-197); T0 = A Z0 + E0 - X
                 # the parameter tables of this call, assembled once (not per layer)

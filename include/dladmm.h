@@ -422,6 +422,46 @@ typedef struct dladmm_safeguard_news_desc {
 int dladmm_safeguard_news_f32(const dladmm_safeguard_news_desc* d, void* stream);
 
 /*
+ * The whole learned + safeguarded KM forward (test_syn_l1l1_scalar.py:178-316) as one kernel
+ * launch: per layer the learned (V4) candidate, the classic KM candidate and the KM step from the
+ * learned candidate, the norm |S|, the mu update and the per-column select of
+ * dladmm_safeguard_f32, with the column state in registers across all layers.  Starts from
+ * mu_0 = |S(Z0, E0, L0, T0, X, E0)|, T0 = A Z0 + E0 - X (stored as T[0]).  Every output is what
+ * `layers` rounds of three one-layer dladmm_fwd_f32 calls (V4 on layer k's row of scalar_params;
+ * V5 with W = A^T on km_params, twice) and dladmm_safeguard_f32 compute, bit for bit while the
+ * decisions agree (the norm is the same fp64 sum in another order).
+ * Shapes: the 256 x 512 register instantiation, fp32; m > 256 or n > 512: DLADMM_E_UNSUPPORTED.
+ * The call enqueues the packs of W_0 .. W_{layers-1}, A and A^T (once each), a fill of count and
+ * the kernel.
+ */
+typedef struct dladmm_lskm_desc {
+  int32_t abi_version;
+  int32_t m, n, batch, layers;
+  const float* X; int64_t ld_x;
+  const float* A; int64_t ld_a;
+  const float* Z0; int64_t ld_z0;
+  const float* E0; int64_t ld_e0;
+  const float* L0; int64_t ld_l0;
+  const float* const* W; int64_t ld_w;  /* host array of `layers` device pointers, n x m each */
+  const float* scalar_params;      /* device [layers][DLADMM_NSCALAR]: the learned layers */
+  const float* km_params;          /* device [DLADMM_NSCALAR], the KM step: BETA1 = BETA2 = BETA3
+                                      = beta, S1 = ss1, THETA_Z = ss1 alpha, SS2 = THETA_E = ss2 */
+  float beta, c;                   /* |S| = sqrt(sum (beta Ts)^2 + (c (Es - 2 El + Ep))^2) */
+  double delta;
+  int32_t updater;                 /* enum dladmm_mu_updater */
+  float mu_param;
+  float *Z, *E, *L;                /* [layers][n | m][ld_out]: the selected state of each layer */
+  float* T;                        /* [layers + 1][m][ld_out] */
+  int64_t ld_out;
+  int32_t* count;                  /* [layers]: safeguarded columns of each layer (overwritten) */
+  float* mu_out;                   /* [batch] mu after the last layer, or NULL */
+  void* workspace; size_t workspace_bytes;
+} dladmm_lskm_desc;
+
+size_t dladmm_lskm_workspace_bytes(const dladmm_lskm_desc* d);
+int dladmm_lskm_f32(const dladmm_lskm_desc* d, void* stream);
+
+/*
  * Per-column evaluation objectives over saved layers: for every
  * layer k and batch column b (fp64 sums over the rows)
  *   reg[k*batch+b] = sum_i |Z_k|,  fit = sum_i |E_k - T_{k+1}| (L1L1) or 0.5 sum (E_k - T_{k+1})^2
