@@ -4,12 +4,14 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <unordered_map>
 #include <vector>
 
 #include "dladmm_common.h"
 #include "dladmm_wgrad_x3.h"
 #include "dladmm_internal.h"
 #include "dladmm_lskm_fused.h"
+#include "dladmm_lskm_news_fused.h"
 
 namespace dladmm {
 
@@ -1527,6 +1529,40 @@ inline size_t lskm_bytes(const dladmm_lskm_desc* d) {
   return align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float)) * (size_t)(2 + d->layers);
 }
 
+// ---- the safeguarded newS LSKM forward as one launch (dladmm_lskm_news_fused.hip)
+// workspace: packed A, packed -A^T, the packed distinct -W (at most `layers` of them), then the
+// device table of the layers' packed weights
+inline int lskm_news_validate(const dladmm_lskm_news_desc* d) {
+  if (!d) return DLADMM_E_NULL;
+  if (d->abi_version != DLADMM_ABI_VERSION) return DLADMM_E_ABI_VERSION;
+  if (d->m < 1 || d->n < 1 || d->batch < 1) return DLADMM_E_SHAPE;
+  if (d->layers < 1 || d->layers > DLADMM_MAX_LAYERS) return DLADMM_E_LAYERS;
+  if (d->m > kShapeMP[2] || d->n > kShapeNP[2]) return DLADMM_E_UNSUPPORTED;
+  if (d->updater < DLADMM_MU_NONE || d->updater > DLADMM_MU_RT) return DLADMM_E_UNSUPPORTED;
+  const void* req[] = {d->X, d->A, d->Z0, d->E0, d->L0, d->W, d->scalar_params, d->km_params,
+                       d->inv_bs, d->Z, d->E, d->L, d->count, d->workspace};
+  for (const void* p : req)
+    if (!p) return DLADMM_E_NULL;
+  for (int k = 0; k < d->layers; ++k)
+    if (!d->W[k]) return DLADMM_E_NULL;
+  const int64_t B = d->batch;
+  if (d->ld_x < B || d->ld_z0 < B || d->ld_e0 < B || d->ld_l0 < B || d->ld_out < B ||
+      d->ld_a < d->n || d->ld_w < d->m)
+    return DLADMM_E_SHAPE;
+  // 32-bit buffer offsets over the instantiation's padded rows (lskm_validate)
+  const int64_t lim = (int64_t)1 << 31, NPs = kShapeNP[2];
+  if (NPs * d->ld_x * 4 >= lim || NPs * d->ld_z0 * 4 >= lim || NPs * d->ld_e0 * 4 >= lim ||
+      NPs * d->ld_l0 * 4 >= lim || NPs * d->ld_out * 4 >= lim)
+    return DLADMM_E_UNSUPPORTED;
+  return 0;
+}
+inline size_t lskm_news_tab_offset(const dladmm_lskm_news_desc* d) {
+  return align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float)) * (size_t)(2 + d->layers);
+}
+inline size_t lskm_news_bytes(const dladmm_lskm_news_desc* d) {
+  return lskm_news_tab_offset(d) + align256((size_t)d->layers * sizeof(const float*));
+}
+
 }  // namespace dladmm
 
 extern "C" {
@@ -1575,6 +1611,67 @@ int dladmm_lskm_f32(const dladmm_lskm_desc* d, void* stream) {
   a.beta = d->beta; a.c = d->c; a.thresh = (float)(1.0 - d->delta);  // python (1.0-delta)
   a.param = d->mu_param; a.updater = d->updater;
   return (int)launch_lskm_fused(a, ceil_div(d->batch, 16), s);
+}
+
+size_t dladmm_lskm_news_workspace_bytes(const dladmm_lskm_news_desc* d) {
+  using namespace dladmm;
+  // sizing needs the shape alone (room for `layers` distinct weights)
+  if (!d || d->abi_version != DLADMM_ABI_VERSION || d->layers < 1 ||
+      d->layers > DLADMM_MAX_LAYERS || d->m < 1 || d->n < 1 || d->m > kShapeMP[2] ||
+      d->n > kShapeNP[2])
+    return 0;
+  return lskm_news_bytes(d);
+}
+
+int dladmm_lskm_news_f32(const dladmm_lskm_news_desc* d, void* stream) {
+  using namespace dladmm;
+  if (int e = lskm_news_validate(d)) return e;
+  const size_t fb = align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float));
+  if (d->workspace_bytes < lskm_news_bytes(d)) return DLADMM_E_WORKSPACE;
+  if (((uintptr_t)d->workspace) & 255) return DLADMM_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)d->workspace;
+  float* Ap = (float*)ws;
+  float* Atp = (float*)(ws + fb);
+  float* Wp = (float*)(ws + 2 * fb);
+  const float** wtab = (const float**)(ws + lskm_news_tab_offset(d));
+  const int MB = kShapeMP[2] / 16, NB = kShapeNP[2] / 16;
+  // each distinct weight once per call (tied: one, partially tied: one per block of layers);
+  // layer k reads the packed copy of its pointer
+  std::vector<const float*> distinct;
+  std::vector<const void*> packed((size_t)d->layers);
+  std::unordered_map<const float*, size_t> slot;
+  for (int k = 0; k < d->layers; ++k) {
+    auto it = slot.find(d->W[k]);
+    if (it == slot.end()) {
+      it = slot.emplace(d->W[k], distinct.size()).first;
+      distinct.push_back(d->W[k]);
+    }
+    packed[(size_t)k] = ws + (2 + it->second) * fb;
+  }
+  if (hipError_t e = pack(distinct.data(), (int)distinct.size(), d->n, d->m, d->ld_w, NB, MB, 2,
+                          Wp, s, -1.0f))
+    return (int)e;
+  const float* asrc[1] = {d->A};
+  if (hipError_t e = pack(asrc, 1, d->m, d->n, d->ld_a, MB, NB, 2, Ap, s)) return (int)e;
+  if (hipError_t e = pack(asrc, 1, d->n, d->m, d->ld_a, NB, MB, 2, Atp, s, -1.0f, nullptr, 1))
+    return (int)e;
+  if (hipError_t e = write_ptr_table(packed.data(), d->layers, (const void**)wtab, s))
+    return (int)e;
+  if (hipError_t e = zero_async(d->count, (size_t)d->layers * sizeof(int32_t), s)) return (int)e;
+  LskmNewsArgs a{};
+  a.m = d->m; a.n = d->n; a.B = d->batch; a.K = d->layers;
+  a.X = d->X; a.ldx = d->ld_x;
+  a.Z0 = d->Z0; a.ldz0 = d->ld_z0;
+  a.E0 = d->E0; a.lde0 = d->ld_e0;
+  a.L0 = d->L0; a.ldl0 = d->ld_l0;
+  a.Ap = Ap; a.Atp = Atp; a.wtab = wtab;
+  a.scal = d->scalar_params; a.km = d->km_params; a.inv_bs = d->inv_bs;
+  a.Zo = d->Z; a.Eo = d->E; a.Lo = d->L; a.ldo = d->ld_out;
+  a.count = d->count; a.mask = d->mask; a.mu_out = d->mu_out;
+  a.thresh = (float)(1.0 - d->delta);  // python (1.0-delta)
+  a.param = d->mu_param; a.updater = d->updater;
+  return (int)launch_lskm_news_fused(a, ceil_div(d->batch, 16), s);
 }
 
 size_t dladmm_lena_workspace_bytes(const dladmm_lena_desc* d) {

@@ -18,7 +18,9 @@ Differences from `lskm.DLADMMNetLSKM` (test_syn_l1l1_scalar.py), all in the refe
 Execution: pure KM of any K (the K = 1,000 ground truth) is ONE V7 launch, re-indexed as
 `DLADMMNetNewS.forward` does; pure learned is the newS forward; `continued` runs its K - layers
 KM steps as one ELZ launch from the last triple; a safeguarded layer is the KM candidate, the
-L2O candidate, the KM step from the L2O candidate (with its tail product) and the select.
+L2O candidate, the KM step from the L2O candidate (with its tail product) and the select -- or,
+with `fused_safeguard=True` at m <= 256, n <= 512, the whole safeguarded loop as one launch of
+`dladmm_lskm_news_f32` (csrc/dladmm_lskm_news_fused.hip), with the same outputs.
 """
 from __future__ import annotations
 
@@ -30,7 +32,7 @@ import torch
 
 from . import _lib
 from .model import (DLADMMNetNewS, DLADMMNetPTiedNewS, DLADMMNetTiedNewS, _scalar_table)
-from .ops import ForwardResult, _PLAN_FLAGS, dladmm_forward
+from .ops import ForwardResult, _PLAN_FLAGS, _f32_dev, _workspace, dladmm_forward
 
 _UPDATERS = {"None": _lib.MU_NONE, "EMA": _lib.MU_EMA, "GS": _lib.MU_GS, "RT": _lib.MU_RT}
 # slots of a table row that belong to the E / L half of a step (the rest: its Z half)
@@ -53,7 +55,11 @@ class _NewSLSKM:
         if mu_k_method not in _UPDATERS:
             raise ValueError(f"unknown mu_k_method {mu_k_method!r}")
 
-    def _init_lskm(self, alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init):
+    def _init_lskm(self, alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init,
+                   fused_safeguard=None):
+        # the safeguarded loop as one launch (dladmm_lskm_news_f32): True requires it; False and
+        # None keep the per-layer launches
+        self.fused_safeguard = fused_safeguard
         # the reference's module globals (test_syn_l1l1_newS.py:39-46)
         self.alpha, self.delta = float(alpha), float(delta)
         self.mu_k_method, self.mu_k_param = mu_k_method, float(mu_k_param)
@@ -178,9 +184,15 @@ class _NewSLSKM:
         return [w.detach() for w in self._weights()]
 
     def forward(self, x, use_learned=False, use_safeguard=False, continued=False,
-                K: Optional[int] = None):
+                K: Optional[int] = None, fused_safeguard: Optional[bool] = None):
         """test_syn_l1l1_newS.py:188-268.  K defaults to the reference's
-        `layers if (not continued and (use_learned or use_safeguard)) else num_iter` (:54)."""
+        `layers if (not continued and (use_learned or use_safeguard)) else num_iter` (:54).
+        fused_safeguard overrides the constructor's setting for this call."""
+        fused = self.fused_safeguard if fused_safeguard is None else fused_safeguard
+        if fused and (self.A.shape[0] > 256 or self.A.shape[1] > 512):
+            raise ValueError(
+                f"dladmm: fused_safeguard=True needs the 256 x 512 register shape (m <= 256, "
+                f"n <= 512), got m={self.A.shape[0]}, n={self.A.shape[1]}")
         if K is None:
             K = self.layers if (not continued and (use_learned or use_safeguard)) else \
                 self.num_iter
@@ -204,7 +216,8 @@ class _NewSLSKM:
                 return self._ret(Z, E, L, None)
             count = None
             if use_safeguard:
-                Z, E, L, count = self._safeguarded(x, nl)
+                Z, E, L, count = (self._safeguarded_fused if fused and x.shape[1] > 0
+                                  else self._safeguarded)(x, nl)
             else:
                 Z, E, L = DLADMMNetNewS.forward(self, x, nl)
                 Z, E, L = list(Z), list(E), list(L)
@@ -259,6 +272,50 @@ class _NewSLSKM:
         return list(Zo), list(Eo), list(Lo), count
 
 
+    def _safeguarded_fused(self, x, nl: int):
+        """dladmm_lskm_news_f32: layers 0 .. nl-1 of the safeguarded loop, one kernel launch."""
+        Lb = _lib.lib()
+        dev = x.device
+        X, A = _f32_dev(x, "X"), _f32_dev(self.A, "A")
+        Z0, E0, L0 = _f32_dev(self.Z0, "Z0"), _f32_dev(self.E0, "E0"), _f32_dev(self.L0, "L0")
+        m, B = X.shape
+        n = A.shape[1]
+        if A.shape[0] != m or tuple(Z0.shape) != (n, B) or tuple(E0.shape) != (m, B) or \
+                tuple(L0.shape) != (m, B):
+            raise RuntimeError("dladmm: Z0/E0/L0 shapes do not broadcast with X")
+        Zo = torch.empty((nl, n, B), device=dev)
+        Eo = torch.empty((nl, m, B), device=dev)
+        Lo = torch.empty((nl, m, B), device=dev)
+        count = torch.zeros(self.layers, dtype=torch.int32, device=dev)
+        mask = torch.zeros((self.layers, B), dtype=torch.uint8, device=dev)
+        # a shared weight is one tensor: its pointer repeats, and the entry packs it once
+        Ws = [_f32_dev(w.contiguous(), f"W[{k}]") for k, w in enumerate(self._l2o_weights()[:nl])]
+        ptab = self._tables(dev)["scalar_params"][:nl].contiguous()
+        km, inv_bs = self._km_table(1), self._inv_bs()
+        warr = _lib.ptr_array([w.data_ptr() for w in Ws])
+        d = _lib.LskmNewsDesc()
+        d.abi_version = _lib.ABI_VERSION
+        d.m, d.n, d.batch, d.layers = m, n, B, nl
+        d.X, d.ld_x = X.data_ptr(), X.stride(0)
+        d.A, d.ld_a = A.data_ptr(), A.stride(0)
+        d.Z0, d.ld_z0 = Z0.data_ptr(), Z0.stride(0)
+        d.E0, d.ld_e0 = E0.data_ptr(), E0.stride(0)
+        d.L0, d.ld_l0 = L0.data_ptr(), L0.stride(0)
+        d.W, d.ld_w = ctypes.cast(warr, ctypes.POINTER(ctypes.c_void_p)), m
+        d.scalar_params, d.km_params, d.inv_bs = ptab.data_ptr(), km.data_ptr(), inv_bs.data_ptr()
+        d.delta = self.delta
+        d.updater, d.mu_param = _UPDATERS[self.mu_k_method], self.mu_k_param
+        d.Z, d.E, d.L, d.ld_out = Zo.data_ptr(), Eo.data_ptr(), Lo.data_ptr(), B
+        d.count, d.mask = count.data_ptr(), mask.data_ptr()
+        wsb = Lb.dladmm_lskm_news_workspace_bytes(ctypes.byref(d))
+        ws = _workspace(dev, max(wsb, 1))
+        d.workspace, d.workspace_bytes = ws.data_ptr(), wsb
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(Lb.dladmm_lskm_news_f32(ctypes.byref(d), ctypes.c_void_p(stream)))
+        self.sg_mask = mask
+        return list(Zo), list(Eo), list(Lo), count
+
+
 class DLADMMNetNewSLSKM(_NewSLSKM, DLADMMNetNewS):
     """test_syn_l1l1_newS.py:75-272; `prepend_init=True` gives test_syn_l1l1_newS_Acols.py's
     return lists (Z0 / E0 / L0 inserted in front)."""
@@ -266,10 +323,12 @@ class DLADMMNetNewSLSKM(_NewSLSKM, DLADMMNetNewS):
 
     def __init__(self, m, n, d, batch_size, A, Z0, E0, L0, layers, *, alpha: float = 0.01,
                  delta: float = -99.0, mu_k_method: str = "None", mu_k_param: float = 0.0,
-                 num_iter: int = 200, prepend_init: Optional[bool] = None):
+                 num_iter: int = 200, prepend_init: Optional[bool] = None,
+                 fused_safeguard: Optional[bool] = None):
         self._check_updater(mu_k_method)
         DLADMMNetNewS.__init__(self, m, n, d, batch_size, A, Z0, E0, L0, layers)
-        self._init_lskm(alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init)
+        self._init_lskm(alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init,
+                        fused_safeguard)
 
 
 class DLADMMNetTiedNewSLSKM(_NewSLSKM, DLADMMNetTiedNewS):
@@ -279,10 +338,12 @@ class DLADMMNetTiedNewSLSKM(_NewSLSKM, DLADMMNetTiedNewS):
 
     def __init__(self, m, n, d, batch_size, A, Z0, E0, L0, layers, *, alpha: float = 0.01,
                  delta: float = -99.0, mu_k_method: str = "None", mu_k_param: float = 0.0,
-                 num_iter: int = 200, prepend_init: Optional[bool] = None):
+                 num_iter: int = 200, prepend_init: Optional[bool] = None,
+                 fused_safeguard: Optional[bool] = None):
         self._check_updater(mu_k_method)
         DLADMMNetTiedNewS.__init__(self, m, n, d, batch_size, A, Z0, E0, L0, layers)
-        self._init_lskm(alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init)
+        self._init_lskm(alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init,
+                        fused_safeguard)
 
 
 class DLADMMNetPTiedNewSLSKM(_NewSLSKM, DLADMMNetPTiedNewS):
@@ -292,7 +353,8 @@ class DLADMMNetPTiedNewSLSKM(_NewSLSKM, DLADMMNetPTiedNewS):
     def __init__(self, m, n, d, batch_size, A, Z0, E0, L0, layers, interval, *,
                  alpha: float = 0.01, delta: float = -99.0, mu_k_method: str = "None",
                  mu_k_param: float = 0.0, num_iter: int = 200,
-                 prepend_init: Optional[bool] = None):
+                 prepend_init: Optional[bool] = None, fused_safeguard: Optional[bool] = None):
         self._check_updater(mu_k_method)
         DLADMMNetPTiedNewS.__init__(self, m, n, d, batch_size, A, Z0, E0, L0, layers, interval)
-        self._init_lskm(alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init)
+        self._init_lskm(alpha, delta, mu_k_method, mu_k_param, num_iter, prepend_init,
+                        fused_safeguard)

@@ -462,6 +462,48 @@ size_t dladmm_lskm_workspace_bytes(const dladmm_lskm_desc* d);
 int dladmm_lskm_f32(const dladmm_lskm_desc* d, void* stream);
 
 /*
+ * The newS scripts' learned + safeguarded KM forward (test_syn_l1l1_newS.py:188-268, its _Acols,
+ * tied and partially tied forms) as one kernel launch: the loop carries (E, L, Z); per layer the
+ * learned candidate (E / L half on the E / L slots of layer k - 1's row of scalar_params, Z half
+ * on layer k's: Z = S(Z - S1_k W_k Var, THETA_Z_k), S1 = 1 for the untied model), the classic V7
+ * candidate on km_params, the KM_ELZ step from the learned candidate, the norm, mu update and
+ * select of dladmm_safeguard_news_f32, with the column state and the product A Z of the current
+ * state in registers across all layers.  Layer 0 is a Z-step only; mu_0 = Snorm_ELZ(E0, L0, Z0, X).
+ * Every output is what the rounds of one-step DLADMM_F_ELZ calls and dladmm_safeguard_news_f32
+ * compute, bit for bit while the decisions agree (the norm is the same fp64 sums in another order).
+ * Shapes: the 256 x 512 register instantiation, fp32; m > 256 or n > 512: DLADMM_E_UNSUPPORTED.
+ * The call enqueues the packs of A, A^T and every distinct W pointer (once each), the table of
+ * the layers' packed weights, a fill of count and the kernel.
+ */
+typedef struct dladmm_lskm_news_desc {
+  int32_t abi_version;
+  int32_t m, n, batch, layers;
+  const float* X; int64_t ld_x;
+  const float* A; int64_t ld_a;
+  const float* Z0; int64_t ld_z0;
+  const float* E0; int64_t ld_e0;
+  const float* L0; int64_t ld_l0;
+  const float* const* W; int64_t ld_w;  /* host array of `layers` device pointers, n x m each;
+                                           entries may repeat (tied / partially tied weights) */
+  const float* scalar_params;      /* device [layers][DLADMM_NSCALAR], unshifted */
+  const float* km_params;          /* device [DLADMM_NSCALAR], the V7 KM step: BETA1 = BETA2 = beta,
+                                      THETA_E = 1 / beta, S1 = ss1, THETA_Z = ss1 alpha */
+  const float* inv_bs;             /* device scalar 1 / (beta ss1) */
+  double delta;
+  int32_t updater;                 /* enum dladmm_mu_updater */
+  float mu_param;
+  float *Z, *E, *L;                /* [layers][n | m][ld_out]: the selected state of each layer */
+  int64_t ld_out;
+  int32_t* count;                  /* [layers]: safeguarded columns of each layer (overwritten) */
+  uint8_t* mask;                   /* [layers][batch] keep decisions, or NULL */
+  float* mu_out;                   /* [batch] mu after the last layer, or NULL */
+  void* workspace; size_t workspace_bytes;
+} dladmm_lskm_news_desc;
+
+size_t dladmm_lskm_news_workspace_bytes(const dladmm_lskm_news_desc* d);
+int dladmm_lskm_news_f32(const dladmm_lskm_news_desc* d, void* stream);
+
+/*
  * Per-column evaluation objectives over saved layers: for every
  * layer k and batch column b (fp64 sums over the rows)
  *   reg[k*batch+b] = sum_i |Z_k|,  fit = sum_i |E_k - T_{k+1}| (L1L1) or 0.5 sum (E_k - T_{k+1})^2
