@@ -12,6 +12,7 @@ from .model import DLADMMNetNewS, DLADMMNetPTiedNewS, DLADMMNetTiedNewS  # noqa:
 from .lskm import DLADMMNetLSKM  # noqa: F401
 from .lskm_news import (DLADMMNetNewSLSKM, DLADMMNetPTiedNewSLSKM,  # noqa: F401
                         DLADMMNetTiedNewSLSKM)
+from .lskm_lena import DLADMMNetLenaLSKM  # noqa: F401
 from .ops import (BackwardResult, ForwardResult, dladmm_backward, dladmm_forward,  # noqa: F401
                   plan_flags)
 
@@ -19,5 +20,6 @@ __all__ = ["DLADMMNet", "DLADMMNetLTheta", "DLADMMNetFull", "DLADMMNetScalar",
            "DLADMMNetScalarSl2", "DLADMMNetScalarZ0",
            "DLADMMNetScalarTied", "DLADMMNetLasso", "DLADMMNetNewS", "DLADMMNetTiedNewS",
            "DLADMMNetPTiedNewS", "DLADMMNetLSKM", "DLADMMNetNewSLSKM",
-           "DLADMMNetTiedNewSLSKM", "DLADMMNetPTiedNewSLSKM", "VARIANTS", "load_checkpoint",
+           "DLADMMNetTiedNewSLSKM", "DLADMMNetPTiedNewSLSKM", "DLADMMNetLenaLSKM", "VARIANTS",
+           "load_checkpoint",
            "dladmm_forward", "dladmm_backward", "ForwardResult", "BackwardResult"]

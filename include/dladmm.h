@@ -504,6 +504,49 @@ size_t dladmm_lskm_news_workspace_bytes(const dladmm_lskm_news_desc* d);
 int dladmm_lskm_news_f32(const dladmm_lskm_news_desc* d, void* stream);
 
 /*
+ * The lena model's (V1) learned + safeguarded KM forward (test_lena_lskm.py:108-188) as one kernel
+ * launch: per layer the learned candidate with the per-sample beta1_k / beta2_k (m x batch, read
+ * per element) and the uniform thresholds of scalar_params, the classic candidate S() (:91-106)
+ * on km_params, the same step from the learned candidate, the norm |T_new| of that step alone
+ * (no E term, no beta factor), the mu update and the per-column select, with the column state in
+ * registers across all layers.  mu_0 = |T_new| of the classic step from (Z0, E0, L0).  T is not
+ * an output.  Every output is what `layers` rounds of a one-layer V1 dladmm_fwd_f32, two one-step
+ * V5 calls with W = A^T on km_params and dladmm_safeguard_f32 (beta = 1, c = 0) compute, bit for
+ * bit while the decisions agree (the norm is the same fp64 sum in another order).
+ * Shapes: the 256 x 512 register instantiation, fp32; m > 256 or n > 512: DLADMM_E_UNSUPPORTED.
+ * The call enqueues the packs of W_0 .. W_{layers-1}, A and A^T (once each), the two device
+ * tables of the layers' beta pointers, a fill of count and the kernel.
+ */
+typedef struct dladmm_lskm_lena_desc {
+  int32_t abi_version;
+  int32_t m, n, batch, layers;
+  const float* X; int64_t ld_x;
+  const float* A; int64_t ld_a;
+  const float* Z0; int64_t ld_z0;
+  const float* E0; int64_t ld_e0;
+  const float* L0; int64_t ld_l0;
+  const float* const* W; int64_t ld_w;  /* host array of `layers` device pointers, n x m each */
+  const float* const* beta1_elem;  /* host arrays of `layers` device pointers, m x batch each, */
+  const float* const* beta2_elem;  /* common row stride ld_beta                                */
+  int64_t ld_beta;
+  const float* scalar_params;      /* device [layers][DLADMM_NSCALAR]: THETA_Z, THETA_E */
+  const float* km_params;          /* device [DLADMM_NSCALAR], the classic step: BETA1 = BETA2 =
+                                      BETA3 = S1 = 1 / sqrt(L), SS2 = THETA_E = ss2,
+                                      THETA_Z = ss1 alpha */
+  double delta;
+  int32_t updater;                 /* enum dladmm_mu_updater */
+  float mu_param;
+  float *Z, *E, *L;                /* [layers][n | m][ld_out]: the selected state of each layer */
+  int64_t ld_out;
+  int32_t* count;                  /* [layers]: safeguarded columns of each layer (overwritten) */
+  float* mu_out;                   /* [batch] mu after the last layer, or NULL */
+  void* workspace; size_t workspace_bytes;
+} dladmm_lskm_lena_desc;
+
+size_t dladmm_lskm_lena_workspace_bytes(const dladmm_lskm_lena_desc* d);
+int dladmm_lskm_lena_f32(const dladmm_lskm_lena_desc* d, void* stream);
+
+/*
  * Per-column evaluation objectives over saved layers: for every
  * layer k and batch column b (fp64 sums over the rows)
  *   reg[k*batch+b] = sum_i |Z_k|,  fit = sum_i |E_k - T_{k+1}| (L1L1) or 0.5 sum (E_k - T_{k+1})^2
