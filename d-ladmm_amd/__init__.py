@@ -13,6 +13,8 @@ from .lskm import DLADMMNetLSKM  # noqa: F401
 from .lskm_news import (DLADMMNetNewSLSKM, DLADMMNetPTiedNewSLSKM,  # noqa: F401
                         DLADMMNetTiedNewSLSKM)
 from .lskm_lena import DLADMMNetLenaLSKM  # noqa: F401
+from .lskm_rowp import (DLADMMNetFullLSKM, DLADMMNetGtLThetaLSKM,  # noqa: F401
+                        DLADMMNetLThetaLSKM)
 from .ops import (BackwardResult, ForwardResult, dladmm_backward, dladmm_forward,  # noqa: F401
                   plan_flags)
 
@@ -20,6 +22,7 @@ __all__ = ["DLADMMNet", "DLADMMNetLTheta", "DLADMMNetFull", "DLADMMNetScalar",
            "DLADMMNetScalarSl2", "DLADMMNetScalarZ0",
            "DLADMMNetScalarTied", "DLADMMNetLasso", "DLADMMNetNewS", "DLADMMNetTiedNewS",
            "DLADMMNetPTiedNewS", "DLADMMNetLSKM", "DLADMMNetNewSLSKM",
-           "DLADMMNetTiedNewSLSKM", "DLADMMNetPTiedNewSLSKM", "DLADMMNetLenaLSKM", "VARIANTS",
+           "DLADMMNetTiedNewSLSKM", "DLADMMNetPTiedNewSLSKM", "DLADMMNetLenaLSKM",
+           "DLADMMNetLThetaLSKM", "DLADMMNetGtLThetaLSKM", "DLADMMNetFullLSKM", "VARIANTS",
            "load_checkpoint",
            "dladmm_forward", "dladmm_backward", "ForwardResult", "BackwardResult"]

@@ -41,7 +41,8 @@ EXPORTED = ("dladmm_abi_version", "dladmm_fwd_workspace_bytes", "dladmm_fwd_path
             "dladmm_safeguard_f32", "dladmm_safeguard_news_f32", "dladmm_colobj_f32", "dladmm_lena_workspace_bytes",
             "dladmm_lena_f32", "dladmm_lskm_workspace_bytes", "dladmm_lskm_f32",
             "dladmm_lskm_news_workspace_bytes", "dladmm_lskm_news_f32",
-            "dladmm_lskm_lena_workspace_bytes", "dladmm_lskm_lena_f32", "dladmm_scale_f32",
+            "dladmm_lskm_lena_workspace_bytes", "dladmm_lskm_lena_f32",
+            "dladmm_lskm_rowp_workspace_bytes", "dladmm_lskm_rowp_f32", "dladmm_scale_f32",
             "dladmm_error_string")
 # enum dladmm_mu_updater
 MU_NONE, MU_EMA, MU_GS, MU_RT = 0, 1, 2, 3
@@ -168,6 +169,23 @@ class LskmLenaDesc(ctypes.Structure):
     ]
 
 
+class LskmRowpDesc(ctypes.Structure):
+    """Mirror of `struct dladmm_lskm_rowp_desc` (include/dladmm.h)."""
+    _fields_ = [
+        ("abi_version", _i32), ("m", _i32), ("n", _i32), ("batch", _i32), ("layers", _i32),
+        ("emode", _i32),
+        ("X", _fp), ("ld_x", _i64), ("A", _fp), ("ld_a", _i64),
+        ("Z0", _fp), ("ld_z0", _i64), ("E0", _fp), ("ld_e0", _i64), ("L0", _fp), ("ld_l0", _i64),
+        ("W", ctypes.POINTER(_fp)), ("ld_w", _i64),
+        ("row_params", _fp), ("row_stride", _i64), ("km_params", _fp),
+        ("beta", ctypes.c_float), ("c", ctypes.c_float), ("delta", ctypes.c_double),
+        ("updater", _i32), ("mu_param", ctypes.c_float),
+        ("Z", _fp), ("E", _fp), ("L", _fp), ("T", _fp), ("ld_out", _i64),
+        ("count", _fp), ("mu_out", _fp),
+        ("workspace", _fp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 class ColObjDesc(ctypes.Structure):
     """Mirror of `struct dladmm_colobj_desc` (include/dladmm.h)."""
     _fields_ = [
@@ -241,6 +259,10 @@ def lib():
     L.dladmm_lskm_lena_workspace_bytes.argtypes = [ctypes.POINTER(LskmLenaDesc)]
     L.dladmm_lskm_lena_f32.restype = ctypes.c_int
     L.dladmm_lskm_lena_f32.argtypes = [ctypes.POINTER(LskmLenaDesc), ctypes.c_void_p]
+    L.dladmm_lskm_rowp_workspace_bytes.restype = ctypes.c_size_t
+    L.dladmm_lskm_rowp_workspace_bytes.argtypes = [ctypes.POINTER(LskmRowpDesc)]
+    L.dladmm_lskm_rowp_f32.restype = ctypes.c_int
+    L.dladmm_lskm_rowp_f32.argtypes = [ctypes.POINTER(LskmRowpDesc), ctypes.c_void_p]
     L.dladmm_colobj_f32.restype = ctypes.c_int
     L.dladmm_colobj_f32.argtypes = [ctypes.POINTER(ColObjDesc), ctypes.c_void_p]
     L.dladmm_lena_workspace_bytes.restype = ctypes.c_size_t

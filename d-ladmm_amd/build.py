@@ -30,6 +30,8 @@ UNITS = ("dladmm_capi.hip", "dladmm_fused.hip", "dladmm_fused_savep.hip",
          "dladmm_lskm_news_fused.hip",
          # the lena (V1) safeguarded LSKM forward as one launch
          "dladmm_lskm_lena_fused.hip",
+         # the per-row models' (V2 / V3) safeguarded LSKM forward as one launch
+         "dladmm_lskm_rowp_fused.hip",
          "dladmm_tile_bf16.hip", "dladmm_wgrad_x3.hip",
          "dladmm_reverse.hip", "dladmm_reverse_rs.hip",
          "dladmm_lena.hip",
@@ -58,6 +60,7 @@ UNIT_FLAGS["dladmm_wgrad_x3.hip"] = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 UNIT_FLAGS["dladmm_lskm_fused.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS["dladmm_lskm_news_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 UNIT_FLAGS["dladmm_lskm_lena_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
+UNIT_FLAGS["dladmm_lskm_rowp_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 # The fused fp32 kernel keeps its whole state in registers; which instantiations take the two-slot
 # weight ring (csrc/dladmm_fused_kernel.h kRing2) rests on a register census.
 # So these units are compiled with the resource-usage remarks, and a kernel of theirs whose
@@ -67,7 +70,7 @@ CENSUS_UNITS = ("dladmm_fused.hip", "dladmm_fused_savep.hip", "dladmm_fused_elz.
                 "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip",
                 # lskm_fused_kernel holds three states per lane: no scratch, ever
                 "dladmm_lskm_fused.hip", "dladmm_lskm_news_fused.hip",
-                "dladmm_lskm_lena_fused.hip")
+                "dladmm_lskm_lena_fused.hip", "dladmm_lskm_rowp_fused.hip")
 SCRATCH_RECORD = {
     "ILi256ELi512ELi1ELi0ELb1ELb0ELb1E": 416,   # V4, ELZ unit
     "ILi256ELi512ELi1ELi3ELb1ELb0ELb1E": 416,   # V5, ELZ unit

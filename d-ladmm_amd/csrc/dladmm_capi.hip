@@ -13,6 +13,7 @@
 #include "dladmm_lskm_fused.h"
 #include "dladmm_lskm_news_fused.h"
 #include "dladmm_lskm_lena_fused.h"
+#include "dladmm_lskm_rowp_fused.h"
 
 namespace dladmm {
 
@@ -1598,6 +1599,37 @@ inline size_t lskm_lena_bytes(const dladmm_lskm_lena_desc* d) {
   return lskm_lena_tab_offset(d) + align256((size_t)(2 * d->layers + 1) * sizeof(const float*));
 }
 
+// ---- the per-row models' (V2 / V3) safeguarded LSKM forward as one launch
+// (dladmm_lskm_rowp_fused.hip); workspace: packed A, packed -A^T, packed -W_0 .. -W_{layers-1}
+inline int lskm_rowp_validate(const dladmm_lskm_rowp_desc* d) {
+  if (!d) return DLADMM_E_NULL;
+  if (d->abi_version != DLADMM_ABI_VERSION) return DLADMM_E_ABI_VERSION;
+  if (d->m < 1 || d->n < 1 || d->batch < 1) return DLADMM_E_SHAPE;
+  if (d->layers < 1 || d->layers > DLADMM_MAX_LAYERS) return DLADMM_E_LAYERS;
+  if (d->m > kShapeMP[2] || d->n > kShapeNP[2]) return DLADMM_E_UNSUPPORTED;
+  if (d->emode != DLADMM_V2_LTHETA && d->emode != DLADMM_V3_FULL) return DLADMM_E_UNSUPPORTED;
+  if (d->updater < DLADMM_MU_NONE || d->updater > DLADMM_MU_RT) return DLADMM_E_UNSUPPORTED;
+  const void* req[] = {d->X, d->A, d->Z0, d->E0, d->L0, d->W, d->row_params, d->km_params,
+                       d->Z, d->E, d->L, d->T, d->count, d->workspace};
+  for (const void* p : req)
+    if (!p) return DLADMM_E_NULL;
+  for (int k = 0; k < d->layers; ++k)
+    if (!d->W[k]) return DLADMM_E_NULL;
+  const int64_t B = d->batch;
+  if (d->ld_x < B || d->ld_z0 < B || d->ld_e0 < B || d->ld_l0 < B || d->ld_out < B ||
+      d->ld_a < d->n || d->ld_w < d->m || d->row_stride < d->m || d->row_stride < d->n)
+    return DLADMM_E_SHAPE;
+  // 32-bit buffer offsets over the instantiation's padded rows (lskm_validate)
+  const int64_t lim = (int64_t)1 << 31, NPs = kShapeNP[2];
+  if (NPs * d->ld_x * 4 >= lim || NPs * d->ld_z0 * 4 >= lim || NPs * d->ld_e0 * 4 >= lim ||
+      NPs * d->ld_l0 * 4 >= lim || NPs * d->ld_out * 4 >= lim)
+    return DLADMM_E_UNSUPPORTED;
+  return 0;
+}
+inline size_t lskm_rowp_bytes(const dladmm_lskm_rowp_desc* d) {
+  return align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float)) * (size_t)(2 + d->layers);
+}
+
 }  // namespace dladmm
 
 extern "C" {
@@ -1762,6 +1794,51 @@ int dladmm_lskm_lena_f32(const dladmm_lskm_lena_desc* d, void* stream) {
   a.thresh = (float)(1.0 - d->delta);  // python (1.0-delta)
   a.param = d->mu_param; a.updater = d->updater;
   return (int)launch_lskm_lena_fused(a, ceil_div(d->batch, 16), s);
+}
+
+size_t dladmm_lskm_rowp_workspace_bytes(const dladmm_lskm_rowp_desc* d) {
+  using namespace dladmm;
+  // sizing needs the shape alone
+  if (!d || d->abi_version != DLADMM_ABI_VERSION || d->layers < 1 ||
+      d->layers > DLADMM_MAX_LAYERS || d->m < 1 || d->n < 1 || d->m > kShapeMP[2] ||
+      d->n > kShapeNP[2])
+    return 0;
+  return lskm_rowp_bytes(d);
+}
+
+int dladmm_lskm_rowp_f32(const dladmm_lskm_rowp_desc* d, void* stream) {
+  using namespace dladmm;
+  if (int e = lskm_rowp_validate(d)) return e;
+  const size_t fb = align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float));
+  if (d->workspace_bytes < lskm_rowp_bytes(d)) return DLADMM_E_WORKSPACE;
+  if (((uintptr_t)d->workspace) & 255) return DLADMM_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)d->workspace;
+  float* Ap = (float*)ws;
+  float* Atp = (float*)(ws + fb);
+  float* Wp = (float*)(ws + 2 * fb);
+  const int MB = kShapeMP[2] / 16, NB = kShapeNP[2] / 16;
+  // every weight once per call: -W_k, A, and -A^T (the transposed read of A)
+  if (hipError_t e = pack(d->W, d->layers, d->n, d->m, d->ld_w, NB, MB, 2, Wp, s, -1.0f))
+    return (int)e;
+  const float* asrc[1] = {d->A};
+  if (hipError_t e = pack(asrc, 1, d->m, d->n, d->ld_a, MB, NB, 2, Ap, s)) return (int)e;
+  if (hipError_t e = pack(asrc, 1, d->n, d->m, d->ld_a, NB, MB, 2, Atp, s, -1.0f, nullptr, 1))
+    return (int)e;
+  if (hipError_t e = zero_async(d->count, (size_t)d->layers * sizeof(int32_t), s)) return (int)e;
+  LskmRowpArgs a{};
+  a.m = d->m; a.n = d->n; a.B = d->batch; a.K = d->layers;
+  a.X = d->X; a.ldx = d->ld_x;
+  a.Z0 = d->Z0; a.ldz0 = d->ld_z0;
+  a.E0 = d->E0; a.lde0 = d->ld_e0;
+  a.L0 = d->L0; a.ldl0 = d->ld_l0;
+  a.Ap = Ap; a.Atp = Atp; a.Wp = Wp;
+  a.rowp = d->row_params; a.rstride = d->row_stride; a.km = d->km_params;
+  a.Zo = d->Z; a.Eo = d->E; a.Lo = d->L; a.To = d->T; a.ldo = d->ld_out;
+  a.count = d->count; a.mu_out = d->mu_out;
+  a.beta = d->beta; a.c = d->c; a.thresh = (float)(1.0 - d->delta);  // python (1.0-delta)
+  a.param = d->mu_param; a.updater = d->updater;
+  return (int)launch_lskm_rowp_fused(d->emode, a, ceil_div(d->batch, 16), s);
 }
 
 size_t dladmm_lena_workspace_bytes(const dladmm_lena_desc* d) {

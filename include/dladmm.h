@@ -547,6 +547,50 @@ size_t dladmm_lskm_lena_workspace_bytes(const dladmm_lskm_lena_desc* d);
 int dladmm_lskm_lena_f32(const dladmm_lskm_lena_desc* d, void* stream);
 
 /*
+ * The per-row models' (V2: test_syn_l1l1_ltheta.py / test_syn_gt_ltheta.py; V3:
+ * test_syn_l1l1_full.py) learned + safeguarded KM forward as one kernel launch: dladmm_lskm_f32
+ * with the learned candidate of variant `emode` on row_params -- per-row beta1, beta2, beta3
+ * (V2: beta1 again), theta_e and V3's ss2 over the m rows, theta_z over the n rows, in
+ * dladmm_fwd_desc's layout [layers][DLADMM_NSCALAR][row_stride] -- staged per layer in LDS.  The
+ * classic candidate, the norm |[beta Ts ; c (Es - 2 El + Ep)]|, mu_0, the mu update, the select
+ * and T[0] = A Z0 + E0 - X are dladmm_lskm_f32's on this call's km_params, beta and c.  Every
+ * output is what `layers` rounds of a one-layer dladmm_fwd_f32 of `emode`, two one-step V5 calls
+ * with W = A^T on km_params and dladmm_safeguard_f32 compute, bit for bit while the decisions
+ * agree (the norm is the same fp64 sum in another order).
+ * Shapes: the 256 x 512 register instantiation, fp32; m > 256 or n > 512: DLADMM_E_UNSUPPORTED.
+ * The call enqueues the packs of W_0 .. W_{layers-1}, A and A^T (once each), a fill of count and
+ * the kernel.
+ */
+typedef struct dladmm_lskm_rowp_desc {
+  int32_t abi_version;
+  int32_t m, n, batch, layers;
+  int32_t emode;                   /* DLADMM_V2_LTHETA or DLADMM_V3_FULL */
+  const float* X; int64_t ld_x;
+  const float* A; int64_t ld_a;
+  const float* Z0; int64_t ld_z0;
+  const float* E0; int64_t ld_e0;
+  const float* L0; int64_t ld_l0;
+  const float* const* W; int64_t ld_w;  /* host array of `layers` device pointers, n x m each */
+  const float* row_params;         /* device [layers][DLADMM_NSCALAR][row_stride] */
+  int64_t row_stride;              /* >= max(m, n) */
+  const float* km_params;          /* device [DLADMM_NSCALAR], the KM step: BETA1 = BETA2 = BETA3
+                                      = beta, S1 = ss1, THETA_Z = ss1 alpha, SS2 = THETA_E = ss2 */
+  float beta, c;                   /* |S| = sqrt(sum (beta Ts)^2 + (c (Es - 2 El + Ep))^2) */
+  double delta;
+  int32_t updater;                 /* enum dladmm_mu_updater */
+  float mu_param;
+  float *Z, *E, *L;                /* [layers][n | m][ld_out]: the selected state of each layer */
+  float* T;                        /* [layers + 1][m][ld_out] */
+  int64_t ld_out;
+  int32_t* count;                  /* [layers]: safeguarded columns of each layer (overwritten) */
+  float* mu_out;                   /* [batch] mu after the last layer, or NULL */
+  void* workspace; size_t workspace_bytes;
+} dladmm_lskm_rowp_desc;
+
+size_t dladmm_lskm_rowp_workspace_bytes(const dladmm_lskm_rowp_desc* d);
+int dladmm_lskm_rowp_f32(const dladmm_lskm_rowp_desc* d, void* stream);
+
+/*
  * Per-column evaluation objectives over saved layers: for every
  * layer k and batch column b (fp64 sums over the rows)
  *   reg[k*batch+b] = sum_i |Z_k|,  fit = sum_i |E_k - T_{k+1}| (L1L1) or 0.5 sum (E_k - T_{k+1})^2
