@@ -42,7 +42,8 @@ EXPORTED = ("dladmm_abi_version", "dladmm_fwd_workspace_bytes", "dladmm_fwd_path
             "dladmm_lena_f32", "dladmm_lskm_workspace_bytes", "dladmm_lskm_f32",
             "dladmm_lskm_news_workspace_bytes", "dladmm_lskm_news_f32",
             "dladmm_lskm_lena_workspace_bytes", "dladmm_lskm_lena_f32",
-            "dladmm_lskm_rowp_workspace_bytes", "dladmm_lskm_rowp_f32", "dladmm_scale_f32",
+            "dladmm_lskm_rowp_workspace_bytes", "dladmm_lskm_rowp_f32",
+            "dladmm_sl2_workspace_bytes", "dladmm_sl2_f32", "dladmm_scale_f32",
             "dladmm_error_string")
 # enum dladmm_mu_updater
 MU_NONE, MU_EMA, MU_GS, MU_RT = 0, 1, 2, 3
@@ -215,6 +216,21 @@ class LenaDesc(ctypes.Structure):
     ]
 
 
+class Sl2Desc(ctypes.Structure):
+    """Mirror of `struct dladmm_sl2_desc` (include/dladmm.h)."""
+    _fields_ = [
+        ("abi_version", _i32), ("m", _i32), ("n", _i32), ("batch", _i32), ("mode", _i32),
+        ("beta", ctypes.c_float), ("ss1", ctypes.c_float), ("ss2", ctypes.c_float),
+        ("thz", ctypes.c_float), ("c", ctypes.c_float),
+        ("X", _fp), ("ld_x", _i64), ("A", _fp), ("ld_a", _i64),
+        ("Z", _fp), ("ld_z", _i64), ("E", _fp), ("ld_e", _i64), ("L", _fp), ("ld_l", _i64),
+        ("T", _fp), ("ld_t", _i64), ("Ep", _fp), ("ld_ep", _i64),
+        ("coef", _fp), ("colsum", _fp), ("total", _fp),
+        ("gZ", _fp), ("gE", _fp), ("gL", _fp), ("gT", _fp), ("gEp", _fp), ("ld_g", _i64),
+        ("workspace", _fp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 _LIB = None
 
 
@@ -269,6 +285,10 @@ def lib():
     L.dladmm_lena_workspace_bytes.argtypes = [ctypes.POINTER(LenaDesc)]
     L.dladmm_lena_f32.restype = ctypes.c_int
     L.dladmm_lena_f32.argtypes = [ctypes.POINTER(LenaDesc), ctypes.c_void_p]
+    L.dladmm_sl2_workspace_bytes.restype = ctypes.c_size_t
+    L.dladmm_sl2_workspace_bytes.argtypes = [ctypes.POINTER(Sl2Desc)]
+    L.dladmm_sl2_f32.restype = ctypes.c_int
+    L.dladmm_sl2_f32.argtypes = [ctypes.POINTER(Sl2Desc), ctypes.c_void_p]
     L.dladmm_scale_f32.restype = ctypes.c_int
     L.dladmm_scale_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
     L.dladmm_error_string.restype = ctypes.c_char_p

@@ -32,6 +32,8 @@ UNITS = ("dladmm_capi.hip", "dladmm_fused.hip", "dladmm_fused_savep.hip",
          "dladmm_lskm_lena_fused.hip",
          # the per-row models' (V2 / V3) safeguarded LSKM forward as one launch
          "dladmm_lskm_rowp_fused.hip",
+         # the S-L2 training term (one KM step, its norm and the norm's adjoint) as one launch
+         "dladmm_sl2.hip",
          "dladmm_tile_bf16.hip", "dladmm_wgrad_x3.hip",
          "dladmm_reverse.hip", "dladmm_reverse_rs.hip",
          "dladmm_lena.hip",
@@ -61,6 +63,7 @@ UNIT_FLAGS["dladmm_lskm_fused.hip"] = ["-Xclang", "-target-feature", "-Xclang", 
 UNIT_FLAGS["dladmm_lskm_news_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 UNIT_FLAGS["dladmm_lskm_lena_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 UNIT_FLAGS["dladmm_lskm_rowp_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
+UNIT_FLAGS["dladmm_sl2.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 # The fused fp32 kernel keeps its whole state in registers; which instantiations take the two-slot
 # weight ring (csrc/dladmm_fused_kernel.h kRing2) rests on a register census.
 # So these units are compiled with the resource-usage remarks, and a kernel of theirs whose
@@ -70,7 +73,9 @@ CENSUS_UNITS = ("dladmm_fused.hip", "dladmm_fused_savep.hip", "dladmm_fused_elz.
                 "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip",
                 # lskm_fused_kernel holds three states per lane: no scratch, ever
                 "dladmm_lskm_fused.hip", "dladmm_lskm_news_fused.hip",
-                "dladmm_lskm_lena_fused.hip", "dladmm_lskm_rowp_fused.hip")
+                "dladmm_lskm_lena_fused.hip", "dladmm_lskm_rowp_fused.hip",
+                # sl2_fused_kernel: no scratch either
+                "dladmm_sl2.hip")
 SCRATCH_RECORD = {
     "ILi256ELi512ELi1ELi0ELb1ELb0ELb1E": 416,   # V4, ELZ unit
     "ILi256ELi512ELi1ELi3ELb1ELb0ELb1E": 416,   # V5, ELZ unit

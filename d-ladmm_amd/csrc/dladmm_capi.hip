@@ -14,6 +14,7 @@
 #include "dladmm_lskm_news_fused.h"
 #include "dladmm_lskm_lena_fused.h"
 #include "dladmm_lskm_rowp_fused.h"
+#include "dladmm_sl2.h"
 
 namespace dladmm {
 
@@ -1630,6 +1631,41 @@ inline size_t lskm_rowp_bytes(const dladmm_lskm_rowp_desc* d) {
   return align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float)) * (size_t)(2 + d->layers);
 }
 
+// ---- the S-L2 training term and its adjoint as one launch (dladmm_sl2.hip)
+// workspace: packed A, packed -A^T
+inline int sl2_validate(const dladmm_sl2_desc* d) {
+  if (!d) return DLADMM_E_NULL;
+  if (d->abi_version != DLADMM_ABI_VERSION) return DLADMM_E_ABI_VERSION;
+  if (d->m < 1 || d->n < 1 || d->batch < 1) return DLADMM_E_SHAPE;
+  if (d->m > kShapeMP[2] || d->n > kShapeNP[2]) return DLADMM_E_UNSUPPORTED;
+  if (d->mode != 0 && d->mode != 1) return DLADMM_E_UNSUPPORTED;
+  // the masks [Zn != 0], [En != 0] are the shrink's derivative for positive thresholds only
+  if (!(d->thz > 0.0f) || !(d->ss2 > 0.0f)) return DLADMM_E_UNSUPPORTED;
+  const void* req[] = {d->X, d->A, d->Z, d->E, d->L, d->T, d->Ep, d->colsum, d->workspace};
+  for (const void* p : req)
+    if (!p) return DLADMM_E_NULL;
+  const int64_t B = d->batch;
+  if (d->ld_x < B || d->ld_z < B || d->ld_e < B || d->ld_l < B || d->ld_t < B || d->ld_ep < B ||
+      d->ld_a < d->n)
+    return DLADMM_E_SHAPE;
+  // 32-bit buffer offsets over the instantiation's padded rows (lskm_validate)
+  const int64_t lim = (int64_t)1 << 31, NPs = kShapeNP[2];
+  if (NPs * d->ld_x * 4 >= lim || NPs * d->ld_z * 4 >= lim || NPs * d->ld_e * 4 >= lim ||
+      NPs * d->ld_l * 4 >= lim || NPs * d->ld_t * 4 >= lim || NPs * d->ld_ep * 4 >= lim)
+    return DLADMM_E_UNSUPPORTED;
+  if (d->mode == 1) {
+    const void* out[] = {d->coef, d->gZ, d->gE, d->gL, d->gT};  // gEp may be null
+    for (const void* p : out)
+      if (!p) return DLADMM_E_NULL;
+    if (d->ld_g < B) return DLADMM_E_SHAPE;
+    if (NPs * d->ld_g * 4 >= lim) return DLADMM_E_UNSUPPORTED;
+  }
+  return 0;
+}
+inline size_t sl2_bytes() {
+  return 2 * align256((size_t)kShapeMP[2] * kShapeNP[2] * sizeof(float));
+}
+
 }  // namespace dladmm
 
 extern "C" {
@@ -1839,6 +1875,48 @@ int dladmm_lskm_rowp_f32(const dladmm_lskm_rowp_desc* d, void* stream) {
   a.beta = d->beta; a.c = d->c; a.thresh = (float)(1.0 - d->delta);  // python (1.0-delta)
   a.param = d->mu_param; a.updater = d->updater;
   return (int)launch_lskm_rowp_fused(d->emode, a, ceil_div(d->batch, 16), s);
+}
+
+size_t dladmm_sl2_workspace_bytes(const dladmm_sl2_desc* d) {
+  using namespace dladmm;
+  // sizing needs the shape alone: the workspace pointer is what the caller is about to allocate
+  if (!d || d->abi_version != DLADMM_ABI_VERSION || d->m < 1 || d->n < 1 ||
+      d->m > kShapeMP[2] || d->n > kShapeNP[2])
+    return 0;
+  return sl2_bytes();
+}
+
+int dladmm_sl2_f32(const dladmm_sl2_desc* d, void* stream) {
+  using namespace dladmm;
+  if (int e = sl2_validate(d)) return e;
+  if (d->workspace_bytes < sl2_bytes()) return DLADMM_E_WORKSPACE;
+  if (((uintptr_t)d->workspace) & 255) return DLADMM_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)d->workspace;
+  float* Ap = (float*)ws;
+  float* Atp = (float*)(ws + sl2_bytes() / 2);
+  const int MB = kShapeMP[2] / 16, NB = kShapeNP[2] / 16;
+  // A, and -A^T (the KM step's weight, the transposed read of A), as dladmm_lskm_f32 packs them
+  const float* asrc[1] = {d->A};
+  if (hipError_t e = pack(asrc, 1, d->m, d->n, d->ld_a, MB, NB, 2, Ap, s)) return (int)e;
+  if (hipError_t e = pack(asrc, 1, d->n, d->m, d->ld_a, NB, MB, 2, Atp, s, -1.0f, nullptr, 1))
+    return (int)e;
+  Sl2Args a{};
+  a.m = d->m; a.n = d->n; a.B = d->batch;
+  a.X = d->X; a.ldx = d->ld_x;
+  a.Z = d->Z; a.ldz = d->ld_z;
+  a.E = d->E; a.lde = d->ld_e;
+  a.L = d->L; a.ldl = d->ld_l;
+  a.T = d->T; a.ldt = d->ld_t;
+  a.Ep = d->Ep; a.ldep = d->ld_ep;
+  a.Ap = Ap; a.Atp = Atp;
+  a.coef = d->coef; a.colsum = d->colsum;
+  a.gZ = d->gZ; a.gE = d->gE; a.gL = d->gL; a.gT = d->gT; a.gEp = d->gEp;
+  a.ldg = d->mode == 1 ? d->ld_g : d->batch;
+  a.beta = d->beta; a.ss1 = d->ss1; a.ss2 = d->ss2; a.thz = d->thz; a.c = d->c;
+  if (hipError_t e = launch_sl2(a, d->mode == 1, ceil_div(d->batch, 16), s)) return (int)e;
+  if (d->total) return (int)launch_sl2_total(d->colsum, d->batch, d->total, s);
+  return 0;
 }
 
 size_t dladmm_lena_workspace_bytes(const dladmm_lena_desc* d) {

@@ -35,7 +35,7 @@ import torch.nn as nn
 
 from . import _lib
 from .ops import (ForwardResult, PrologueCache, dladmm_backward, dladmm_forward, dladmm_lena,
-                  dladmm_scale_)
+                  dladmm_scale_, dladmm_sl2)
 
 
 def _dev(t: torch.Tensor) -> torch.Tensor:
@@ -291,7 +291,7 @@ class _DLADMMBase(nn.Module):
 
     def training_loss(self, x, alpha: float, coeffs=None, kind: str = "l1l1",
                       batch: Optional[int] = None, cols=None, lx_sign: float = 1.0,
-                      save_cotangents: bool = True):
+                      save_cotangents: bool = True, lam: float = 1e-4):
         """The reference training objective as one fused, differentiable op:
             total = sum_k coeffs[k] * (alpha * sum(|Z_k|,0).mean() + sum(|X - A Z_k|,0).mean())
         (main_syn_l1l1_scalar.py:283-296; kind='lasso': 0.5*sum((X - A Z_k)^2,0), lasso
@@ -307,6 +307,14 @@ class _DLADMMBase(nn.Module):
         forward forms in the same pass as the sums (2 K m B fp32 beside the saved layers, outside
         save_for_backward: saved-tensor hooks do not see them); save_cotangents=False forms them
         in the backward instead (one more pass over the K products A^T L_k).
+        kind='sl2' (V4: DLADMMNetScalar, ...Sl2, ...Z0; V3: DLADMMNetFull -- the models of
+        main_syn_l1l1-sl2_scalar.py / main_syn_l1l1-sl2_full.py, :263-274) adds to the last
+        layer's l1l1 term
+            lam * squared_two_norm(S(Z[K-1], E[K-1], L[K-1], T[K], X, Ep)).mean(),
+        Ep = E[K-2] (E0 when K == 1): S (:146-157) runs one classic KM step (:117-143) with the
+        scripts' beta = 1, ss1 = 0.5 / ||A^T A||_2, ss2 = 0.3 from the network's last state, in
+        one kernel with its adjoint (ops.dladmm_sl2); per_layer[K-1] includes the term, as the
+        script's loss[k] does; m <= 256, n <= 512.
         Returns (total, per-layer losses [K]); call total.backward() as the reference does.
         Mathematically the same gradients as building the loss from forward()'s outputs with
         torch ops, without the K products A Z_k.
@@ -320,8 +328,11 @@ class _DLADMMBase(nn.Module):
         coeffs = [1.0] * K if coeffs is None else [float(c) for c in coeffs]
         if len(coeffs) != K:
             raise ValueError(f"dladmm: coeffs must have {K} entries")
-        if kind not in ("l1l1", "lasso", "lena"):
+        if kind not in ("l1l1", "lasso", "lena", "sl2"):
             raise ValueError(f"dladmm: unknown loss kind {kind!r}")
+        if kind == "sl2" and (self.m > 256 or self.d > 512):
+            raise ValueError(f"dladmm: kind='sl2' supports m <= 256, n <= 512 "
+                             f"(got m={self.m}, n={self.d})")
         if cols is not None and self.batch_shard is not None:
             raise ValueError("dladmm: cols= slices a replicated model; a batch shard "
                              "(shard_batch_) takes its own columns' x directly")
@@ -336,6 +347,24 @@ class _DLADMMBase(nn.Module):
                 raise ValueError(f"dladmm: cols {cols} do not match x {tuple(x.shape)} and the "
                                  f"model's batch of {self.Z0.shape[1]} columns")
         denom = float(batch if batch is not None else x.shape[1])
+        if kind == "sl2":
+            ncol = self.Z0.shape[1] if cols is None else cols[1] - cols[0]
+            if x.dim() != 2 or tuple(x.shape) != (self.m, ncol):
+                raise ValueError(f"dladmm: kind='sl2' needs x ({self.m}, {ncol}), got "
+                                 f"{tuple(x.shape)}")
+            if self._needs_grad():
+                if x.requires_grad:
+                    raise RuntimeError("dladmm: gradients w.r.t. the input X are not supported")
+                return _DLADMMSl2LossFunction.apply(self, x, coeffs, float(alpha), float(lam),
+                                                    denom, cols, *self.parameters())
+            # evaluation: the module's own precision, nothing saved, the sums only (mode 0)
+            with torch.no_grad():
+                r = self._run_shard(x, cols, loss_kind=_lib.LOSS_L1L1, want_T=True)
+                tot = torch.empty((1,), device=x.device, dtype=torch.float64)
+                _sl2_term(self, x, r, cols, float(alpha), None, tot)
+                per_layer = _sl2_per_layer(r.loss_sums, tot, float(alpha), float(lam), denom)
+                c = _coef_tensor(coeffs, per_layer.device)
+                return (c * per_layer).sum().to(torch.float32), per_layer.to(torch.float32)
         if kind == "lena":
             lx_sign = float(lx_sign)
             if lx_sign not in (1.0, -1.0):
@@ -365,6 +394,18 @@ class _DLADMMBase(nn.Module):
         per_layer = (alpha * r.loss_sums[:, 0] + r.loss_sums[:, 1]) / denom
         c = _coef_tensor(coeffs, per_layer.device)
         return (c * per_layer).sum().to(torch.float32), per_layer.to(torch.float32)
+
+    def _sl2_consts(self) -> dict:
+        """beta, ss1, ss2 of the scripts' S (main_syn_l1l1-sl2_scalar.py:146-149), with
+        L = ||A^T A||_2 computed once as the reference's constructor does (:30-31: numpy on the
+        host, rounded to fp32)."""
+        key = (self.A.data_ptr(), self.A._version)
+        if getattr(self, "_sl2_key", None) != key:
+            a = self.A.detach().cpu().numpy()
+            lip = np.float32(np.linalg.norm(np.matmul(a.transpose(), a), ord=2))
+            self._sl2_c = {"beta": 1.0, "ss1": float(np.float32(0.5) / lip), "ss2": 0.3}
+            self._sl2_key = key
+        return self._sl2_c
 
     def _init_state(self, cols=None):
         """(Z0, E0, L0) of the whole model batch or of the column shard cols = (c0, c1)."""
@@ -669,6 +710,95 @@ class _DLADMMLenaLossFunction(torch.autograd.Function):
         grads = mod._param_grads(res, K, reach, ctx.cols)
         names = [n_ for n_, _ in mod.named_parameters()]
         return (None,) * 8 + tuple(grads.get(n_) for n_ in names)
+
+
+class _DLADMMSl2LossFunction(torch.autograd.Function):
+    """The training objective of main_syn_l1l1-sl2_scalar.py / -sl2_full.py (:255-278) as one
+    differentiable op:
+        total = sum_k coeffs[k] * l1l1_k + coeffs[K-1] * lam * mean_b |S[:, b]|^2,
+    S = S(Z[K-1], E[K-1], L[K-1], T[K], X, Ep) (:146-157).  Forward: the fused K-layer kernel with
+    its L1L1 sums, then dladmm_sl2_f32 in its adjoint form: the per-column norms and, from the
+    same KM step, the cotangents of the term w.r.t. Z[K-1], E[K-1], L[K-1], T[K] and E[K-2].
+    Backward: those cotangents times the upstream gradient (dladmm_scale_f32: no pass at all for
+    total.backward()'s 1) into one dladmm_bwd_f32 call beside the fused L1L1 coefficients.  The
+    reference instead runs S as four more GEMMs and a dozen elementwise passes in torch ops, and
+    autograd as many more.  Outputs: total (0-dim) and the per-layer losses [K]
+    (non-differentiable; [K-1] includes the term)."""
+
+    @staticmethod
+    def forward(ctx, mod, x, coeffs, alpha, lam, denom, cols, *params):
+        dev = mod.A.device
+        tables = mod._tables(dev, cols)
+        W = [w.detach() for w in mod._weights()]
+        Z0, E0, L0 = mod._init_state(cols)
+        r = dladmm_forward(mod.VARIANT, x, mod.A, W, Z0, E0, L0, keep_all=True, want_T=True,
+                           loss_kind=_lib.LOSS_L1L1, want_P=True, precision=_train_precision(mod),
+                           p0_cache=mod._p0_cache(), **tables)
+        c = _coef_tensor(coeffs, dev)
+        # the term's coefficient per unit upstream gradient: coeffs[K-1] * lam / denom
+        w = _coef_tensor((coeffs[-1] * lam / denom,), dev).to(torch.float32)
+        tot = torch.empty((1,), device=dev, dtype=torch.float64)
+        ctx.cot = _sl2_term(mod, x, r, cols, alpha, w, tot)
+        per_layer = _sl2_per_layer(r.loss_sums, tot, alpha, lam, denom)
+        total = (c * per_layer).sum().to(torch.float32)
+        ctx.mod, ctx.tables, ctx.W, ctx.cols = mod, tables, W, cols
+        ctx.alpha, ctx.w = alpha, w
+        ctx.base = torch.stack([c * alpha / denom, c / denom], 1).to(torch.float32)
+        ctx.fpath = r.path  # the forward's kernel path (4: split-f16, see dladmm_backward)
+        ctx.fflags = r.flags  # its plan options: the backward runs on an autograd thread
+        ctx.save_for_backward(x, r.Z, r.E, r.L, r.T, r.P)
+        per_layer = per_layer.to(torch.float32)
+        ctx.mark_non_differentiable(per_layer)
+        return total, per_layer
+
+    @staticmethod
+    def backward(ctx, g_total, g_layers):
+        x, Z, E, L, T, P = ctx.saved_tensors
+        mod = ctx.mod
+        K = mod.layers
+        saved = ForwardResult(Z, E, L, T, None, P=P, path=ctx.fpath, flags=ctx.fflags)
+        cot, ctx.cot = ctx.cot, None
+        if cot is None:
+            # a second backward through a retained graph: the first scaled the forward's
+            # cotangents in place, so form them again
+            cot = _sl2_term(mod, x, saved, ctx.cols, ctx.alpha, ctx.w, None)
+        g1 = g_total.to(torch.float32).reshape(1).contiguous()
+        for g in cot:
+            if g is not None:
+                dladmm_scale_(g, g1)   # a launch that returns at once for total.backward()'s 1
+        gZ, gE, gL, gT, gEp = cot
+        none = [None] * (K - 1)
+        coef = (ctx.base * g_total).contiguous()  # device-side scale, no host sync
+        Z0, E0, L0 = mod._init_state(ctx.cols)
+        res = dladmm_backward(mod.VARIANT, x, mod.A, ctx.W, Z0, E0, L0, saved,
+                              gZ=none + [gZ], gE=(none[1:] + [gEp] if K > 1 else []) + [gE],
+                              gL=none + [gL], gT=[None] * K + [gT],
+                              loss_kind=_lib.LOSS_L1L1, loss_coef=coef,
+                              tied=mod._shared_weight(), **ctx.tables)
+        # S reads E[K-1], L[K-1] and T[K]: every layer step feeds the objective
+        reach = {"z": [True] * K, "e": [True] * K, "l": [True] * K}
+        grads = mod._param_grads(res, K, reach, ctx.cols)
+        names = [n for n, _ in mod.named_parameters()]
+        return (None,) * 7 + tuple(grads.get(n) for n in names)
+
+
+def _sl2_term(mod, x, r, cols, alpha, w, tot):
+    """dladmm_sl2 on the last state of the forward result r: with w (the adjoint form) returns
+    the five cotangents [gZ, gE, gL, gT, gEp] of w * sum_b |S[:, b]|^2 (gEp None when K == 1:
+    Ep = E0 is no saved layer); tot receives the fixed-order sum of the norms."""
+    K = r.Z.shape[0]
+    Ep = r.E[K - 2] if K > 1 else mod._init_state(cols)[1]
+    out = dladmm_sl2(x, mod.A, r.Z[K - 1], r.E[K - 1], r.L[K - 1], r.T[K], Ep, alpha=alpha,
+                     coef=w, want_gEp=K > 1, total=tot, **mod._sl2_consts())
+    return None if w is None else list(out[1:])
+
+
+def _sl2_per_layer(loss_sums, tot, alpha, lam, denom):
+    """fp64 [K] per-layer losses of main_syn_l1l1-sl2_scalar.py:270-275: the L1L1 terms and, on
+    the last layer, lam * mean_b |S[:, b]|^2 (tot: the sum over the columns, fp64 [1])."""
+    per_layer = (alpha * loss_sums[:, 0] + loss_sums[:, 1]) / denom
+    per_layer[-1:] += tot * (lam / denom)
+    return per_layer
 
 
 def _lena_per_layer(loss_sums, sums, alpha, shape, denom, lx_sign):

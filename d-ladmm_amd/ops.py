@@ -530,6 +530,83 @@ def dladmm_lena(X: torch.Tensor, A: torch.Tensor, E: torch.Tensor, L: torch.Tens
     return out
 
 
+def dladmm_sl2(X: torch.Tensor, A: torch.Tensor, Z: torch.Tensor, E: torch.Tensor,
+               L: torch.Tensor, T: torch.Tensor, Ep: torch.Tensor, *, beta: float, ss1: float,
+               ss2: float, alpha: float, coef: Optional[torch.Tensor] = None,
+               want_gEp: bool = True, total: Optional[torch.Tensor] = None):
+    """The S-L2 training term of main_syn_l1l1-sl2_scalar.py / -sl2_full.py (:263-274) through
+    `dladmm_sl2_f32` (include/dladmm.h, csrc/dladmm_sl2.hip): one classic KM step (:117-143) from
+    a forward's last state Z = Z[K-1] (n, B), E = E[K-1], L = L[K-1], T = T[K], with Ep = E[K-2]
+    (E0 when K == 1) (m, B each), and the squared norm of S = [beta Tn; c (En - 2 E + Ep)]
+    (:146-157), c = sqrt(beta ss2 / (1 - beta ss2)), per column.
+    coef None (mode 0): returns the sums, fp64 [B].  coef = a one-element fp32 device tensor
+    (mode 1): returns (sums, gZ, gE, gL, gT, gEp), the cotangents of coef * sums.sum() w.r.t. the
+    five state operands -- what dladmm_backward takes as gZ[K-1], gE[K-1], gL[K-1], gT[K] and
+    gE[K-2]; want_gEp=False (Ep is no saved layer) skips that store and returns None for it.
+    total: a one-element fp64 device tensor that receives sums.sum() in a fixed order.
+    The thresholds ss1 * alpha and ss2 must be positive; m <= 256 and n <= 512."""
+    Lb = _lib.lib()
+    m, B = X.shape
+    n = A.shape[1]
+    dev = X.device
+    if tuple(A.shape) != (m, n) or tuple(Z.shape) != (n, B) or \
+            any(tuple(t.shape) != (m, B) for t in (E, L, T, Ep)):
+        raise ValueError(f"dladmm: sl2 needs A ({m}, n), Z (n, {B}) and E, L, T, Ep ({m}, {B}); "
+                         f"got A {tuple(A.shape)}, Z {tuple(Z.shape)}, "
+                         f"{[tuple(t.shape) for t in (E, L, T, Ep)]}")
+    if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32
+                                 for t in (X, A, Z, E, L, T, Ep)):
+        raise ValueError("dladmm: sl2 operands must be fp32 tensors on one GPU")
+    c1 = float(beta) * float(ss2)
+    if not 0.0 < c1 < 1.0:
+        raise ValueError(f"dladmm: sl2 needs 0 < beta * ss2 < 1 (got {c1})")
+    if m > 256 or n > 512:
+        raise ValueError(f"dladmm: the fused S-L2 term supports m <= 256, n <= 512 "
+                         f"(got m={m}, n={n})")
+    sums = torch.empty((B,), device=dev, dtype=torch.float64)
+    grads = None
+    if coef is not None:
+        if coef.numel() != 1 or coef.dtype != torch.float32 or coef.device != dev:
+            raise ValueError("dladmm: coef must be a one-element fp32 device tensor")
+        grads = [torch.empty((n, B), device=dev, dtype=torch.float32)] + \
+                [torch.empty((m, B), device=dev, dtype=torch.float32)
+                 for _ in range(4 if want_gEp else 3)] + ([] if want_gEp else [None])
+    if total is not None and (total.numel() != 1 or total.dtype != torch.float64 or
+                              total.device != dev):
+        raise ValueError("dladmm: total must be a one-element fp64 device tensor")
+    if B == 0:
+        if total is not None:
+            total.zero_()
+        return sums if coef is None else (sums, *grads)
+    ops = [t if t.stride(-1) == 1 else t.contiguous() for t in (X, A, Z, E, L, T, Ep)]
+    X, A, Z, E, L, T, Ep = ops
+    d = _lib.Sl2Desc()
+    d.abi_version = _lib.ABI_VERSION
+    d.m, d.n, d.batch = m, n, B
+    d.beta, d.ss1, d.ss2 = float(beta), float(ss1), float(ss2)
+    # ss1 * alpha as the reference forms it: an fp32 tensor times a python scalar (:129)
+    d.thz = float(torch.tensor(float(ss1), dtype=torch.float32) * float(alpha))
+    d.c = (c1 / (1.0 - c1)) ** 0.5
+    for nm, ld, t in (("X", "ld_x", X), ("A", "ld_a", A), ("Z", "ld_z", Z), ("E", "ld_e", E),
+                      ("L", "ld_l", L), ("T", "ld_t", T), ("Ep", "ld_ep", Ep)):
+        setattr(d, nm, t.data_ptr())
+        setattr(d, ld, t.stride(0))
+    d.colsum = sums.data_ptr()
+    d.total = total.data_ptr() if total is not None else None
+    if coef is not None:
+        coef = coef.contiguous()
+        d.mode, d.coef, d.ld_g = 1, coef.data_ptr(), B
+        d.gZ, d.gE, d.gL, d.gT = (g.data_ptr() for g in grads[:4])
+        d.gEp = grads[4].data_ptr() if want_gEp else None
+    wsb = Lb.dladmm_sl2_workspace_bytes(ctypes.byref(d))
+    ws = _workspace(dev, wsb)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), wsb
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(Lb.dladmm_sl2_f32(ctypes.byref(d), ctypes.c_void_p(stream)))
+    del ops
+    return sums if coef is None else (sums, *grads)
+
+
 _WS: "OrderedDict" = None
 _WS_PER_DEVICE = 4   # streams whose workspace stays cached per device (least recently used out)
 

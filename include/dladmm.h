@@ -656,6 +656,50 @@ typedef struct dladmm_lena_desc {
 size_t dladmm_lena_workspace_bytes(const dladmm_lena_desc* d);
 int dladmm_lena_f32(const dladmm_lena_desc* d, void* stream);
 
+/*
+ * The S-L2 training term of main_syn_l1l1-sl2_scalar.py / main_syn_l1l1-sl2_full.py (:263-274)
+ * and its adjoint as one kernel launch.  From a forward's last state Z = Z[K-1], E = E[K-1],
+ * L = L[K-1], T = T[K] and Ep = E[K-2] (E0 when K == 1), one classic KM step (:117-143)
+ *   Zn = S(Z - ss1 A^T (L + beta T), thz),  TTn = A Zn + E - X,
+ *   En = S(E - ss2 (L + beta TTn), ss2),    Tn = A Zn + En - X,
+ * S = [beta Tn ; c (En - 2 E + Ep)] (:146-157), S(., t) = relu(. - t) - relu(-. - t), and
+ *   mode 0: colsum[b] = |S[:, b]|^2 (fp64, fixed order) and, if total is not NULL, their sum
+ *           (fixed order);
+ *   mode 1: also the cotangents of (*coef) * sum_b colsum[b] with respect to Z (gZ, n x batch),
+ *           E, L, T and Ep (gE, gL, gT, gEp, m x batch; row stride ld_g) -- what a dladmm_bwd_f32
+ *           call takes as gZ[K-1], gE[K-1], gL[K-1], gT[K] and gE[K-2].  gEp may be NULL (Ep is
+ *           no saved layer); the same sums as mode 0, bit for bit.
+ * The shrink masks are [Zn != 0] and [En != 0], autograd's for positive thresholds: thz <= 0 or
+ * ss2 <= 0 is DLADMM_E_UNSUPPORTED.
+ * Shapes: the 256 x 512 register instantiation, fp32; m > 256 or n > 512: DLADMM_E_UNSUPPORTED.
+ * The call enqueues the packs of A and A^T, the kernel and (total) a one-wave sum.
+ */
+typedef struct dladmm_sl2_desc {
+  int32_t abi_version;
+  int32_t m, n, batch;
+  int32_t mode;
+  float beta, ss1, ss2;
+  float thz;                       /* the Z-step's threshold, ss1 alpha */
+  float c;                         /* sqrt(beta ss2 / (1 - beta ss2)) */
+  const float* X; int64_t ld_x;
+  const float* A; int64_t ld_a;
+  const float* Z; int64_t ld_z;    /* n x batch */
+  const float* E; int64_t ld_e;    /* m x batch, as L, T and Ep */
+  const float* L; int64_t ld_l;
+  const float* T; int64_t ld_t;
+  const float* Ep; int64_t ld_ep;
+  const float* coef;               /* mode 1: device scalar */
+  double* colsum;                  /* [batch] */
+  double* total;                   /* [1] or NULL */
+  float *gZ, *gE, *gL, *gT;        /* mode 1 */
+  float* gEp;                      /* mode 1, or NULL */
+  int64_t ld_g;
+  void* workspace; size_t workspace_bytes;
+} dladmm_sl2_desc;
+
+size_t dladmm_sl2_workspace_bytes(const dladmm_sl2_desc* d);
+int dladmm_sl2_f32(const dladmm_sl2_desc* d, void* stream);
+
 /* x[0 .. n) *= *s on `stream`, unless *s == 1 (s: a device scalar, read on the device). */
 int dladmm_scale_f32(float* x, int64_t n, const float* s, void* stream);
 
