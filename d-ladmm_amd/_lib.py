@@ -43,7 +43,8 @@ EXPORTED = ("dladmm_abi_version", "dladmm_fwd_workspace_bytes", "dladmm_fwd_path
             "dladmm_lskm_news_workspace_bytes", "dladmm_lskm_news_f32",
             "dladmm_lskm_lena_workspace_bytes", "dladmm_lskm_lena_f32",
             "dladmm_lskm_rowp_workspace_bytes", "dladmm_lskm_rowp_f32",
-            "dladmm_sl2_workspace_bytes", "dladmm_sl2_f32", "dladmm_scale_f32",
+            "dladmm_sl2_workspace_bytes", "dladmm_sl2_f32",
+            "dladmm_elemloss_workspace_bytes", "dladmm_elemloss_f32", "dladmm_scale_f32",
             "dladmm_error_string")
 # enum dladmm_mu_updater
 MU_NONE, MU_EMA, MU_GS, MU_RT = 0, 1, 2, 3
@@ -231,6 +232,21 @@ class Sl2Desc(ctypes.Structure):
     ]
 
 
+class ElemLossDesc(ctypes.Structure):
+    """Mirror of `struct dladmm_elemloss_desc` (include/dladmm.h)."""
+    _fields_ = [
+        ("abi_version", _i32), ("m", _i32), ("n", _i32), ("batch", _i32), ("layers", _i32),
+        ("power", _i32), ("mode", _i32),
+        ("Z", _fp), ("z_layer_stride", _i64), ("ld_z", _i64),
+        ("E", _fp), ("e_layer_stride", _i64), ("ld_e", _i64),
+        ("Zref", _fp), ("ld_zref", _i64), ("Eref", _fp), ("ld_eref", _i64),
+        ("w", _fp), ("want", _fp), ("colsum", _fp), ("total", _fp),
+        ("gZ", _fp), ("gz_layer_stride", _i64), ("gE", _fp), ("ge_layer_stride", _i64),
+        ("ld_g", _i64),
+        ("workspace", _fp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 _LIB = None
 
 
@@ -289,6 +305,10 @@ def lib():
     L.dladmm_sl2_workspace_bytes.argtypes = [ctypes.POINTER(Sl2Desc)]
     L.dladmm_sl2_f32.restype = ctypes.c_int
     L.dladmm_sl2_f32.argtypes = [ctypes.POINTER(Sl2Desc), ctypes.c_void_p]
+    L.dladmm_elemloss_workspace_bytes.restype = ctypes.c_size_t
+    L.dladmm_elemloss_workspace_bytes.argtypes = [ctypes.POINTER(ElemLossDesc)]
+    L.dladmm_elemloss_f32.restype = ctypes.c_int
+    L.dladmm_elemloss_f32.argtypes = [ctypes.POINTER(ElemLossDesc), ctypes.c_void_p]
     L.dladmm_scale_f32.restype = ctypes.c_int
     L.dladmm_scale_f32.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
     L.dladmm_error_string.restype = ctypes.c_char_p

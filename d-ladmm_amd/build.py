@@ -34,6 +34,8 @@ UNITS = ("dladmm_capi.hip", "dladmm_fused.hip", "dladmm_fused_savep.hip",
          "dladmm_lskm_rowp_fused.hip",
          # the S-L2 training term (one KM step, its norm and the norm's adjoint) as one launch
          "dladmm_sl2.hip",
+         # the supervised / reweighted element-wise terms and their seeds, every layer in one launch
+         "dladmm_elemloss.hip",
          "dladmm_tile_bf16.hip", "dladmm_wgrad_x3.hip",
          "dladmm_reverse.hip", "dladmm_reverse_rs.hip",
          "dladmm_lena.hip",
@@ -64,6 +66,7 @@ UNIT_FLAGS["dladmm_lskm_news_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 UNIT_FLAGS["dladmm_lskm_lena_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 UNIT_FLAGS["dladmm_lskm_rowp_fused.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 UNIT_FLAGS["dladmm_sl2.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
+UNIT_FLAGS["dladmm_elemloss.hip"] = UNIT_FLAGS["dladmm_lskm_fused.hip"]
 # The fused fp32 kernel keeps its whole state in registers; which instantiations take the two-slot
 # weight ring (csrc/dladmm_fused_kernel.h kRing2) rests on a register census.
 # So these units are compiled with the resource-usage remarks, and a kernel of theirs whose
@@ -75,7 +78,9 @@ CENSUS_UNITS = ("dladmm_fused.hip", "dladmm_fused_savep.hip", "dladmm_fused_elz.
                 "dladmm_lskm_fused.hip", "dladmm_lskm_news_fused.hip",
                 "dladmm_lskm_lena_fused.hip", "dladmm_lskm_rowp_fused.hip",
                 # sl2_fused_kernel: no scratch either
-                "dladmm_sl2.hip")
+                "dladmm_sl2.hip",
+                # elemloss_fused_kernel: references and two layers' rows in registers, no scratch
+                "dladmm_elemloss.hip")
 SCRATCH_RECORD = {
     "ILi256ELi512ELi1ELi0ELb1ELb0ELb1E": 416,   # V4, ELZ unit
     "ILi256ELi512ELi1ELi3ELb1ELb0ELb1E": 416,   # V5, ELZ unit

@@ -35,7 +35,7 @@ import torch.nn as nn
 
 from . import _lib
 from .ops import (ForwardResult, PrologueCache, dladmm_backward, dladmm_forward, dladmm_lena,
-                  dladmm_scale_, dladmm_sl2)
+                  dladmm_elemloss, dladmm_scale_, dladmm_sl2)
 
 
 def _dev(t: torch.Tensor) -> torch.Tensor:
@@ -291,7 +291,8 @@ class _DLADMMBase(nn.Module):
 
     def training_loss(self, x, alpha: float, coeffs=None, kind: str = "l1l1",
                       batch: Optional[int] = None, cols=None, lx_sign: float = 1.0,
-                      save_cotangents: bool = True, lam: float = 1e-4):
+                      save_cotangents: bool = True, lam: float = 1e-4, z_label=None,
+                      e_label=None, reduction: str = "sum"):
         """The reference training objective as one fused, differentiable op:
             total = sum_k coeffs[k] * (alpha * sum(|Z_k|,0).mean() + sum(|X - A Z_k|,0).mean())
         (main_syn_l1l1_scalar.py:283-296; kind='lasso': 0.5*sum((X - A Z_k)^2,0), lasso
@@ -315,6 +316,18 @@ class _DLADMMBase(nn.Module):
         scripts' beta = 1, ss1 = 0.5 / ||A^T A||_2, ss2 = 0.3 from the network's last state, in
         one kernel with its adjoint (ops.dladmm_sl2); per_layer[K-1] includes the term, as the
         script's loss[k] does; m <= 256, n <= 512.
+        kind='gt' (every model, any shape): the supervised loss against the labels z_label
+        (d, columns) and e_label (m, columns),
+            l_k = (sum((Z_k - z_label)**2) + sum((E_k - e_label)**2)) / denom,
+        reduction='sum' (denom 1: main_syn_gt.py:243-248, main_syn_gt_ltheta.py:243-246) or
+        'mean' (denom = batch: the *_newS_layerwise.py scripts' --loss-fn gt,
+        sum(..., dim=0).mean(), with coeffs [0, ..., 0, 1] for their last-layer form).
+        kind='rw' (every model, any shape): main_syn_l1l1_rw_ltheta.py:236-238,
+            l_k = alpha * mean|Z_k| + mean|E_k|,
+        the means over all elements; pass the script's 0.05 * (k + 1) as coeffs.
+        Both run the sums and the cotangent seeds of all K layers as one streaming kernel
+        (ops.dladmm_elemloss); a layer whose coefficient is 0 gets no cotangent, and a parameter
+        no cotangent reaches gets no gradient (None), as in reference autograd.
         Returns (total, per-layer losses [K]); call total.backward() as the reference does.
         Mathematically the same gradients as building the loss from forward()'s outputs with
         torch ops, without the K products A Z_k.
@@ -328,8 +341,20 @@ class _DLADMMBase(nn.Module):
         coeffs = [1.0] * K if coeffs is None else [float(c) for c in coeffs]
         if len(coeffs) != K:
             raise ValueError(f"dladmm: coeffs must have {K} entries")
-        if kind not in ("l1l1", "lasso", "lena", "sl2"):
+        if kind not in ("l1l1", "lasso", "lena", "sl2", "gt", "rw"):
             raise ValueError(f"dladmm: unknown loss kind {kind!r}")
+        if reduction not in ("sum", "mean"):
+            raise ValueError(f"dladmm: reduction must be 'sum' or 'mean' (got {reduction!r})")
+        if kind != "gt" and (z_label is not None or e_label is not None):
+            raise ValueError(f"dladmm: z_label / e_label belong to kind='gt', not {kind!r}")
+        if kind == "gt":
+            if z_label is None or e_label is None:
+                raise ValueError("dladmm: kind='gt' needs z_label and e_label")
+            want = ((self.d, x.shape[-1]), (self.m, x.shape[-1]))
+            got = (tuple(z_label.shape), tuple(e_label.shape))
+            if got != want:
+                raise ValueError(f"dladmm: kind='gt' needs z_label {want[0]} and e_label "
+                                 f"{want[1]} (the columns of x), got {got[0]} and {got[1]}")
         if kind == "sl2" and (self.m > 256 or self.d > 512):
             raise ValueError(f"dladmm: kind='sl2' supports m <= 256, n <= 512 "
                              f"(got m={self.m}, n={self.d})")
@@ -363,6 +388,22 @@ class _DLADMMBase(nn.Module):
                 tot = torch.empty((1,), device=x.device, dtype=torch.float64)
                 _sl2_term(self, x, r, cols, float(alpha), None, tot)
                 per_layer = _sl2_per_layer(r.loss_sums, tot, float(alpha), float(lam), denom)
+                c = _coef_tensor(coeffs, per_layer.device)
+                return (c * per_layer).sum().to(torch.float32), per_layer.to(torch.float32)
+        if kind in ("gt", "rw"):
+            if kind == "gt" and reduction == "sum":
+                denom = 1.0
+            if self._needs_grad():
+                if x.requires_grad:
+                    raise RuntimeError("dladmm: gradients w.r.t. the input X are not supported")
+                return _DLADMMElemLossFunction.apply(self, x, coeffs, float(alpha), kind, denom,
+                                                     cols, z_label, e_label, *self.parameters())
+            # evaluation: the module's own precision, nothing saved, the sums-only form
+            with torch.no_grad():
+                r = self._run_shard(x, cols, want_T=False,
+                                    loss_kind=_lib.LOSS_L1L1 if kind == "rw" else 0)
+                per_layer = _elem_term(kind, r, z_label, e_label, float(alpha), denom, None,
+                                       None)[0]
                 c = _coef_tensor(coeffs, per_layer.device)
                 return (c * per_layer).sum().to(torch.float32), per_layer.to(torch.float32)
         if kind == "lena":
@@ -780,6 +821,99 @@ class _DLADMMSl2LossFunction(torch.autograd.Function):
         grads = mod._param_grads(res, K, reach, ctx.cols)
         names = [n for n, _ in mod.named_parameters()]
         return (None,) * 7 + tuple(grads.get(n) for n in names)
+
+
+class _DLADMMElemLossFunction(torch.autograd.Function):
+    """The supervised (kind 'gt': main_syn_gt.py:243-248, main_syn_gt_ltheta.py:243-246, the
+    layerwise scripts' --loss-fn gt) and reweighted (kind 'rw': main_syn_l1l1_rw_ltheta.py
+    :236-238) training objectives as one differentiable op.  Forward: the training forward, then
+    dladmm_elemloss_f32 in its adjoint form: the per-layer sums and, in the same pass over the
+    K layers, the cotangents of sum_k coeffs[k] l_k w.r.t. Z_k / E_k, for the layers with a
+    nonzero coefficient only.  Backward: those cotangents times the upstream gradient
+    (dladmm_scale_f32: no pass at all for total.backward()'s 1) into one dladmm_bwd_f32 call;
+    'rw' leaves alpha mean|Z_k| to the forward's own sums and the backward's fused |Z| term, as
+    kind='lena' does.  The reference instead builds the loss from the 2 K returned tensors with
+    four to six torch ops per layer, and autograd as many more.  Outputs: total (0-dim) and the
+    per-layer losses [K] (non-differentiable)."""
+
+    @staticmethod
+    def forward(ctx, mod, x, coeffs, alpha, kind, denom, cols, z_label, e_label, *params):
+        dev = mod.A.device
+        tables = mod._tables(dev, cols)
+        W = [w.detach() for w in mod._weights()]
+        Z0, E0, L0 = mod._init_state(cols)
+        r = dladmm_forward(mod.VARIANT, x, mod.A, W, Z0, E0, L0, keep_all=True, want_T=True,
+                           loss_kind=_lib.LOSS_L1L1 if kind == "rw" else 0, want_P=True,
+                           precision=_train_precision(mod), p0_cache=mod._p0_cache(), **tables)
+        c = _coef_tensor(coeffs, dev)
+        m, n = mod.A.shape
+        # the cotangent coefficient per layer and unit upstream gradient
+        ctx.w = (c / ((m if kind == "rw" else 1) * denom)).to(torch.float32)
+        ctx.want = [ck != 0.0 for ck in coeffs]
+        per_layer, ctx.cot = _elem_term(kind, r, z_label, e_label, alpha, denom, ctx.w, ctx.want)
+        total = (c * per_layer).sum().to(torch.float32)
+        ctx.mod, ctx.tables, ctx.W, ctx.cols, ctx.kind = mod, tables, W, cols, kind
+        ctx.alpha, ctx.denom = alpha, denom
+        # 'rw': (cz_k, 0) of the backward's fused |Z| term
+        ctx.base = torch.stack([c * (alpha / (n * denom)), torch.zeros_like(c)],
+                               1).to(torch.float32) if kind == "rw" else None
+        ctx.fpath = r.path  # the forward's kernel path (4: split-f16, see dladmm_backward)
+        ctx.fflags = r.flags  # its plan options: the backward runs on an autograd thread
+        ctx.save_for_backward(x, r.Z, r.E, r.L, r.T, r.P, z_label, e_label)
+        per_layer = per_layer.to(torch.float32)
+        ctx.mark_non_differentiable(per_layer)
+        return total, per_layer
+
+    @staticmethod
+    def backward(ctx, g_total, g_layers):
+        x, Z, E, L, T, P, z_label, e_label = ctx.saved_tensors
+        mod = ctx.mod
+        K = mod.layers
+        saved = ForwardResult(Z, E, L, T, None, P=P, path=ctx.fpath, flags=ctx.fflags)
+        cot, ctx.cot = ctx.cot, None
+        if cot is None:
+            # a second backward through a retained graph: the first scaled the forward's
+            # cotangents in place, so form them again
+            cot = _elem_term(ctx.kind, saved, z_label, e_label, ctx.alpha, ctx.denom, ctx.w,
+                             ctx.want, losses=False)[1]
+        g1 = g_total.to(torch.float32).reshape(1).contiguous()
+        for g in cot:
+            if g is not None:
+                dladmm_scale_(g, g1)   # a launch that returns at once for total.backward()'s 1
+        gZ, gE = ([g[k] if wk else None for k, wk in enumerate(ctx.want)] if g is not None
+                  else [None] * K for g in cot)
+        kw = {}
+        if ctx.kind == "rw":
+            kw = dict(loss_kind=_lib.LOSS_L1L1, loss_coef=(ctx.base * g_total).contiguous())
+        Z0, E0, L0 = mod._init_state(ctx.cols)
+        res = dladmm_backward(mod.VARIANT, x, mod.A, ctx.W, Z0, E0, L0, saved, gZ=gZ, gE=gE,
+                              tied=mod._shared_weight(), **ctx.tables, **kw)
+        # both kinds read Z_k and E_k of the layers with a nonzero coefficient
+        mark = [True if wk else None for wk in ctx.want]
+        reach = _reachable(K, mark + mark + [None] * K, False)
+        grads = mod._param_grads(res, K, reach, ctx.cols)
+        names = [n for n, _ in mod.named_parameters()]
+        return (None,) * 9 + tuple(grads.get(n) for n in names)
+
+
+def _elem_term(kind, r, z_label, e_label, alpha, denom, w, want, losses=True):
+    """dladmm_elemloss over the forward result r: the fp64 [K] per-layer losses of kind 'gt' /
+    'rw' (None with losses=False: a second backward wants the cotangents alone, and its r has
+    no loss_sums) and, with w (the adjoint form), the cotangent stacks [gZ, gE] (gZ None for
+    'rw': its |Z| term is the backward's fused one)."""
+    K, n = r.Z.shape[0], r.Z.shape[1]
+    m = r.E.shape[1]
+    tot = torch.empty((K, 2), device=r.Z.device, dtype=torch.float64) if losses else None
+    per_layer = None
+    if kind == "gt":
+        out = dladmm_elemloss(r.Z, r.E, z_label, e_label, power=2, coef=w, want=want, total=tot)
+        if losses:
+            per_layer = (tot[:, 0] + tot[:, 1]) / denom
+    else:
+        out = dladmm_elemloss(None, r.E, None, None, power=1, coef=w, want=want, total=tot)
+        if losses:
+            per_layer = alpha * r.loss_sums[:, 0] / (n * denom) + tot[:, 1] / (m * denom)
+    return per_layer, (None if w is None else [out[1], out[2]])
 
 
 def _sl2_term(mod, x, r, cols, alpha, w, tot):

@@ -607,6 +607,96 @@ def dladmm_sl2(X: torch.Tensor, A: torch.Tensor, Z: torch.Tensor, E: torch.Tenso
     return sums if coef is None else (sums, *grads)
 
 
+def dladmm_elemloss(Z: Optional[torch.Tensor], E: Optional[torch.Tensor],
+                    Zref: Optional[torch.Tensor], Eref: Optional[torch.Tensor], *, power: int,
+                    coef: Optional[torch.Tensor] = None, want: Optional[Sequence] = None,
+                    total: Optional[torch.Tensor] = None):
+    """The element-wise training terms of the supervised and reweighted scripts over a forward's
+    stacked outputs Z (K, n, B) and E (K, m, B) through `dladmm_elemloss_f32` (include/dladmm.h,
+    csrc/dladmm_elemloss.hip), every layer in one launch.  power=2: (V_k - Vref)^2
+    (main_syn_gt.py:243-248); power=1: |V_k - Vref| (main_syn_l1l1_rw_ltheta.py:236-238).  Either
+    stack may be None (its sums are 0); Zref (n, B) / Eref (m, B) None means zero.  Views are
+    taken as they are as long as the batch is contiguous.
+    coef None: returns the fp64 (K, 2, B) column sums ([:, 0] the Z part, [:, 1] the E part).
+    coef = device fp32 (K,): returns (sums, gZ, gE), the cotangent stacks of
+    sum_k coef[k] * (sums[k].sum()) -- what dladmm_backward takes as gZ[k] / gE[k] (None for a
+    missing stack).  want: K booleans on the host; layers marked False are not stored (their
+    slices are uninitialised).  total: an fp64 (K, 2) device tensor that receives sums.sum(-1)
+    in a fixed order.  Same inputs, same bits: the reduction order is fixed."""
+    Lb = _lib.lib()
+    if power not in (1, 2):
+        raise ValueError(f"dladmm: elemloss power must be 1 or 2 (got {power})")
+    if Z is None and E is None:
+        raise ValueError("dladmm: elemloss needs Z or E")
+    first = Z if Z is not None else E
+    K, _, B = first.shape
+    dev = first.device
+    for nm, t, ref in (("Z", Z, Zref), ("E", E, Eref)):
+        if t is None:
+            continue
+        if t.dim() != 3 or t.shape[0] != K or t.shape[2] != B or t.dtype != torch.float32 or \
+                t.device != dev or dev.type != "cuda":
+            raise ValueError(f"dladmm: elemloss {nm} must be an fp32 (K, rows, B) GPU tensor")
+        if ref is not None and (tuple(ref.shape) != tuple(t.shape[1:]) or
+                                ref.dtype != torch.float32 or ref.device != dev):
+            raise ValueError(f"dladmm: elemloss {nm}ref must be an fp32 {tuple(t.shape[1:])} "
+                             f"tensor on {dev}, got {tuple(ref.shape)} {ref.dtype} {ref.device}")
+    n = Z.shape[1] if Z is not None else 1
+    m = E.shape[1] if E is not None else 1
+    sums = torch.empty((K, 2, B), device=dev, dtype=torch.float64)
+    gZ = gE = None
+    if coef is not None:
+        if tuple(coef.shape) != (K,) or coef.dtype != torch.float32 or coef.device != dev:
+            raise ValueError("dladmm: coef must be an fp32 (K,) device tensor")
+        if want is not None and len(want) != K:
+            raise ValueError(f"dladmm: want must have {K} entries")
+        gZ = torch.empty((K, n, B), device=dev, dtype=torch.float32) if Z is not None else None
+        gE = torch.empty((K, m, B), device=dev, dtype=torch.float32) if E is not None else None
+    if total is not None and (tuple(total.shape) != (K, 2) or total.dtype != torch.float64 or
+                              total.device != dev or not total.is_contiguous()):
+        raise ValueError("dladmm: total must be a contiguous fp64 (K, 2) device tensor")
+    if K == 0 or B == 0:
+        if total is not None:
+            total.zero_()
+        return sums if coef is None else (sums, gZ, gE)
+
+    def rows_view(t):   # batch contiguous, non-negative strides; otherwise a copy
+        return t if t is None or (t.stride(-1) == 1 and min(t.stride()) >= 0) else t.contiguous()
+    Z, E, Zref, Eref = (rows_view(t) for t in (Z, E, Zref, Eref))
+    d = _lib.ElemLossDesc()
+    d.abi_version = _lib.ABI_VERSION
+    d.m, d.n, d.batch, d.layers = m, n, B, K
+    d.power, d.mode = int(power), 0 if coef is None else 1
+    if Z is not None:
+        d.Z, d.z_layer_stride, d.ld_z = Z.data_ptr(), Z.stride(0), Z.stride(1)
+    if E is not None:
+        d.E, d.e_layer_stride, d.ld_e = E.data_ptr(), E.stride(0), E.stride(1)
+    if Zref is not None and Z is not None:
+        d.Zref, d.ld_zref = Zref.data_ptr(), Zref.stride(0)
+    if Eref is not None and E is not None:
+        d.Eref, d.ld_eref = Eref.data_ptr(), Eref.stride(0)
+    d.colsum = sums.data_ptr()
+    d.total = total.data_ptr() if total is not None else None
+    keep = None
+    if coef is not None:
+        coef = coef.contiguous()
+        d.w, d.ld_g = coef.data_ptr(), B
+        if want is not None:
+            keep = (ctypes.c_uint8 * K)(*[1 if x else 0 for x in want])
+            d.want = ctypes.cast(keep, ctypes.c_void_p)
+        if gZ is not None:
+            d.gZ, d.gz_layer_stride = gZ.data_ptr(), n * B
+        if gE is not None:
+            d.gE, d.ge_layer_stride = gE.data_ptr(), m * B
+    wsb = Lb.dladmm_elemloss_workspace_bytes(ctypes.byref(d))
+    ws = _workspace(dev, wsb)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), wsb
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(Lb.dladmm_elemloss_f32(ctypes.byref(d), ctypes.c_void_p(stream)))
+    del keep
+    return sums if coef is None else (sums, gZ, gE)
+
+
 _WS: "OrderedDict" = None
 _WS_PER_DEVICE = 4   # streams whose workspace stays cached per device (least recently used out)
 

@@ -700,6 +700,52 @@ typedef struct dladmm_sl2_desc {
 size_t dladmm_sl2_workspace_bytes(const dladmm_sl2_desc* d);
 int dladmm_sl2_f32(const dladmm_sl2_desc* d, void* stream);
 
+/*
+ * The element-wise training terms of the supervised and reweighted scripts over a forward's
+ * stacked outputs, every layer in one streaming launch (csrc/dladmm_elemloss.hip):
+ *   power 2 (main_syn_gt.py:243-248, main_syn_gt_ltheta.py:243-246, --loss-fn gt of the
+ *            *_newS_layerwise.py scripts):  (V_k - Vref)^2
+ *   power 1 (main_syn_l1l1_rw_ltheta.py:236-238):  |V_k - Vref|
+ * for V = Z (n x batch per layer, layer k at Z + k*z_layer_stride, row stride ld_z) and V = E
+ * (m x batch).  Either of Z, E may be NULL (its sums are 0); Zref / Eref NULL means zero.  The
+ * difference is formed in fp32, as the reference's subtraction; squares and sums are fp64 in a
+ * fixed order (bitwise repeatable, no atomics).
+ *   mode 0: colsum[(k*2 + t)*batch + b], t = 0 the Z part and 1 the E part, of layer k and column
+ *           b; if total is not NULL, total[k*2 + t] = their sum over b;
+ *   mode 1: also the cotangents of sum_k w[k] * (the two sums of layer k):
+ *           gZ_k = 2 w[k] (Z_k - Zref)  /  w[k] sgn(Z_k - Zref)  (sgn(0) = 0, torch.abs's
+ *           derivative), likewise gE_k, at gZ + k*gz_layer_stride (row stride ld_g) -- what a
+ *           dladmm_bwd_f32 call takes as gZ[k] / gE[k].  w: device [layers].  want: HOST
+ *           [layers], nonzero = layer k's cotangents are stored (others are left untouched);
+ *           NULL = every layer.  The same sums as mode 0, bit for bit.
+ * Any m, n, batch whose operands fit 32-bit byte offsets ((max(m, n) + 68) * ld * 4 < 2^31)
+ * and whose row slabs (32 rows of n + m below batch 2048, 64 from there) and 2 * layers each fit
+ * a grid dimension (65535); otherwise DLADMM_E_UNSUPPORTED.  The workspace holds the row slabs'
+ * fp64 column partials.  Past 64 layers each further 64 take a launch of their own, which reads
+ * the references again.
+ */
+typedef struct dladmm_elemloss_desc {
+  int32_t abi_version;
+  int32_t m, n, batch, layers;
+  int32_t power;                   /* 2: square; 1: absolute value */
+  int32_t mode;
+  const float* Z; int64_t z_layer_stride; int64_t ld_z;
+  const float* E; int64_t e_layer_stride; int64_t ld_e;
+  const float* Zref; int64_t ld_zref;              /* n x batch or NULL */
+  const float* Eref; int64_t ld_eref;              /* m x batch or NULL */
+  const float* w;                  /* mode 1: device [layers] */
+  const uint8_t* want;             /* mode 1: host [layers] or NULL */
+  double* colsum;                  /* [layers][2][batch] */
+  double* total;                   /* [layers][2] or NULL */
+  float* gZ; int64_t gz_layer_stride;              /* mode 1 (with Z) */
+  float* gE; int64_t ge_layer_stride;              /* mode 1 (with E) */
+  int64_t ld_g;
+  void* workspace; size_t workspace_bytes;
+} dladmm_elemloss_desc;
+
+size_t dladmm_elemloss_workspace_bytes(const dladmm_elemloss_desc* d);
+int dladmm_elemloss_f32(const dladmm_elemloss_desc* d, void* stream);
+
 /* x[0 .. n) *= *s on `stream`, unless *s == 1 (s: a device scalar, read on the device). */
 int dladmm_scale_f32(float* x, int64_t n, const float* s, void* stream);
 
