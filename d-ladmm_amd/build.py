@@ -23,6 +23,8 @@ UNITS = ("dladmm_capi.hip", "dladmm_fused.hip", "dladmm_fused_savep.hip",
          # the fused kernel's load-P0 form (inference / training) and the P0 producer
          "dladmm_fused_p0.hip", "dladmm_fused_p0_savep.hip", "dladmm_fused_x3.hip",
          "dladmm_fused_x3_savep.hip", "dladmm_fused_rs.hip", "dladmm_fused_xs.hip",
+         # the bf16-operand fused forward (path 7)
+         "dladmm_fused_bf16.hip",
          "dladmm_layered.hip", "dladmm_backward.hip", "dladmm_lskm.hip", "dladmm_eval.hip",
          # the safeguarded LSKM forward as one launch
          "dladmm_lskm_fused.hip",
@@ -56,7 +58,8 @@ FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", f"--offload-arch={AR
 # MFMAs (packed v_pk_* f32 ops issue slower there; MI355X_MICROARCH.md, price of one filler
 # beside MFMAs)
 UNIT_FLAGS = {u: ["-fno-slp-vectorize"] for u in UNITS
-              if u.startswith("dladmm_fused_x3") or u.startswith("dladmm_reverse")}
+              if u.startswith("dladmm_fused_x3") or u.startswith("dladmm_reverse")
+              or u == "dladmm_fused_bf16.hip"}
 # the split-f16 weight gradient unscales every MFMA result with VALU: MFMA results in VGPRs
 # (no v_accvgpr_read per element)
 UNIT_FLAGS["dladmm_wgrad_x3.hip"] = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
@@ -80,7 +83,9 @@ CENSUS_UNITS = ("dladmm_fused.hip", "dladmm_fused_savep.hip", "dladmm_fused_elz.
                 # sl2_fused_kernel: no scratch either
                 "dladmm_sl2.hip",
                 # elemloss_fused_kernel: references and two layers' rows in registers, no scratch
-                "dladmm_elemloss.hip")
+                "dladmm_elemloss.hip",
+                # bf16_fused_kernel: fp32 Z, E, L and both bf16 operands in registers, no scratch
+                "dladmm_fused_bf16.hip")
 SCRATCH_RECORD = {
     "ILi256ELi512ELi1ELi0ELb1ELb0ELb1E": 416,   # V4, ELZ unit
     "ILi256ELi512ELi1ELi3ELb1ELb0ELb1E": 416,   # V5, ELZ unit

@@ -32,7 +32,8 @@ struct PackArgs {
   const float* scal;   // device [T][DLADMM_NSCALAR] (V4-V6 s1) or null
   int trans;           // 1: pack the transpose (element (row, c) = src[c][row])
   int t0;              // scal row of source t is t0 + t
-  int bf16;            // 1: v_mfma_f32_16x16x32_bf16 A fragments (16 x 32, 8 bf16 per lane)
+  int bf16;            // 1: v_mfma_f32_16x16x32_bf16 A fragments (16 x 32, 8 bf16 per lane);
+                       // 2: the same in the fused bf16 kernel's k order (path 7)
   int vec;             // 1: every source 16-B aligned and ld % 4 == 0: a lane's in-range
                        // piece is read with 16-B loads (the same values, fewer instructions)
 };
@@ -56,6 +57,17 @@ __global__ __launch_bounds__(256) void pack_frags_kernel(const PackArgs p) {
     const int c8 = 32 * jb + 8 * (lane >> 4);
     const float* s8 = p.src[t];
     bf16x8 v;
+    if (p.bf16 == 2) {
+      // element q = column 32 jb + 16 (q >> 2) + 4 (l >> 4) + (q & 3): the k order in which the
+      // state registers of two consecutive 16-row blocks form one B operand (path 7)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int c = 32 * jb + 16 * (q >> 2) + 4 * (lane >> 4) + (q & 3);
+        v[q] = (__bf16)((row < p.R && c < p.C) ? f * s8[(int64_t)row * p.ld + c] : 0.0f);
+      }
+      reinterpret_cast<bf16x8*>(p.dst)[((int64_t)t * p.RB * p.CB + fr) * 64 + lane] = v;
+      return;
+    }
     if (p.vec && !p.trans && row < p.R && c8 + 8 <= p.C) {
       const f32x4* q4 = reinterpret_cast<const f32x4*>(s8 + (int64_t)row * p.ld + c8);
       const f32x4 lo = q4[0], hi = q4[1];
@@ -330,7 +342,8 @@ inline int pick_shape(int m, int n) {
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 struct Plan {
-  int path;  // 1 fused, 2 per-layer, 3 bf16 tiles, 4 fused split-f16, 5 fused row-split
+  int path;  // 1 fused, 2 per-layer, 3 bf16 tiles, 4 fused split-f16, 5 fused row-split, 6 its
+             // four-workgroup form, 7 fused bf16
   // fused
   int shape, MP, NP, tiles;
   // per-layer
@@ -501,6 +514,27 @@ inline int make_plan(const dladmm_fwd_desc* d, Plan* p) {
     p->off_zw = p->off_umax + align256((size_t)(nw + 1) * sizeof(unsigned));
     const bool lean = !d->keep_all && K > 1;
     p->off_loss = p->off_zw + (lean ? align256((size_t)2 * d->n * p->ldzw * sizeof(float)) : 0);
+    p->off_btab = p->off_loss + align256((size_t)2 * K * p->nslots * sizeof(float));
+    p->total = p->off_btab +
+               (d->variant == DLADMM_V1_LENA ? align256((size_t)2 * K * sizeof(void*)) : 0);
+    return 0;
+  }
+  // bf16 fused kernel (opt-in): register-resident shapes, V1 / V4 / V5 / V6, the 16-byte row
+  // layout of its tile stores; every other bf16 call keeps the tile kernels (path 3)
+  if (s >= 0 && fits_32bit(d) && !force_layered && bf16 && (d->flags & DLADMM_F_BF16_FUSED) &&
+      bf16_fused_supports(d->variant) && x3_layout_ok(d)) {
+    p->path = 7;
+    p->shape = s < 1 ? 1 : s;  // the kernel's smallest instantiation is shape 1
+    p->MP = kShapeMP[p->shape];
+    p->NP = kShapeNP[p->shape];
+    p->tiles = ceil_div(d->batch, kTileCols);
+    p->ldl = p->tiles * kTileCols;
+    p->nslots = p->ldl;
+    const size_t tb = (size_t)p->MP * p->NP * 2;  // one packed bf16 tensor
+    p->off_ap = 0;
+    p->off_wp = align256(tb);
+    // fp32 Z stays in registers: lean mode needs no workspace of its own
+    p->off_loss = p->off_wp + align256(tb * (shared_weight(d) ? 1 : K));
     p->off_btab = p->off_loss + align256((size_t)2 * K * p->nslots * sizeof(float));
     p->total = p->off_btab +
                (d->variant == DLADMM_V1_LENA ? align256((size_t)2 * K * sizeof(void*)) : 0);
@@ -768,6 +802,53 @@ inline int run_fused_x3(const dladmm_fwd_desc* d, const Plan& p, char* ws, hipSt
   if (hipError_t e = (savep ? launch_fused_x3_shape_savep : launch_fused_x3_shape)(
           p.shape, d->variant, a, p.tiles, s))
     return (int)e;
+  if (d->ev_kernel_stop) {
+    if (hipError_t e = hipEventRecord((hipEvent_t)d->ev_kernel_stop, s)) return (int)e;
+  }
+  return 0;
+}
+
+// path 7: pack A and every -W_k as bf16 fragments in the kernel's k order (one per k-step,
+// zero-padded to MP x NP), then the one launch
+inline int run_fused_bf16(const dladmm_fwd_desc* d, const Plan& p, char* ws, hipStream_t s) {
+  float* Ap = (float*)(ws + p.off_ap);
+  float* Wp = (float*)(ws + p.off_wp);
+  const int MB = p.MP / 16, NB = p.NP / 16, KS1 = p.MP / 32, KS2 = p.NP / 32;
+  const bool shared = shared_weight(d);
+  const float* asrc[1] = {d->A};
+  if (hipError_t e = pack(asrc, 1, d->m, d->n, d->ld_a, MB, KS2, 0, Ap, s, 1.0f, nullptr, 0, 0, 2))
+    return (int)e;
+  if (hipError_t e = pack(d->W, shared ? 1 : d->layers, d->n, d->m, d->ld_w, NB, KS1, 0, Wp, s,
+                          -1.0f, nullptr, 0, 0, 2))
+    return (int)e;
+  FusedArgs a{};
+  a.m = d->m; a.n = d->n; a.B = d->batch; a.K = d->layers;
+  a.keep_all = d->keep_all ? 1 : 0; a.loss_kind = d->loss_kind; a.ldl = p.ldl;
+  a.X = d->X; a.ldx = d->ld_x;
+  a.Z0 = d->Z0; a.ldz0 = d->ld_z0;
+  a.E0 = d->E0; a.lde0 = d->ld_e0;
+  a.L0 = d->L0; a.ldl0 = d->ld_l0;
+  a.Ap = Ap; a.Wp = Wp;
+  a.wstep = shared ? 0 : 1;
+  a.scal = d->scalar_params;
+  a.Zo = d->Z; a.Eo = d->E; a.Lo = d->L; a.To = d->T; a.ldo = d->ld_out;
+  a.lossp = (float*)(ws + p.off_loss);
+  if (d->variant == DLADMM_V1_LENA) {
+    // V1: the per-layer beta pointers as device tables (scalar-loaded per G2 pass, any depth)
+    a.ldb = d->ld_beta;
+    const void** tab = (const void**)(ws + p.off_btab);
+    if (hipError_t e = write_ptr_table((const void* const*)d->beta1_elem, d->layers, tab, s))
+      return (int)e;
+    if (hipError_t e = write_ptr_table((const void* const*)d->beta2_elem, d->layers,
+                                       tab + d->layers, s))
+      return (int)e;
+    a.b1t = (const float* const*)tab;
+    a.b2t = (const float* const*)(tab + d->layers);
+  }
+  if (d->ev_kernel_start) {
+    if (hipError_t e = hipEventRecord((hipEvent_t)d->ev_kernel_start, s)) return (int)e;
+  }
+  if (hipError_t e = launch_fused_bf16_shape(p.shape, d->variant, a, p.tiles, s)) return (int)e;
   if (d->ev_kernel_stop) {
     if (hipError_t e = hipEventRecord((hipEvent_t)d->ev_kernel_stop, s)) return (int)e;
   }
@@ -2006,8 +2087,9 @@ int dladmm_fwd_f32(const dladmm_fwd_desc* d, void* stream) {
   if (((uintptr_t)d->workspace) & 255) return DLADMM_E_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)d->workspace;
-  const int rc = p.path == 1 || p.path >= 5 ? run_fused(d, p, ws, s)
+  const int rc = p.path == 1 || p.path == 5 || p.path == 6 ? run_fused(d, p, ws, s)
                  : p.path == 4 ? run_fused_x3(d, p, ws, s)
+                 : p.path == 7 ? run_fused_bf16(d, p, ws, s)
                                : run_layered(d, p, ws, s);
   if (rc) return rc;
   // per-layer loss sums, fixed-order fp64 reduction of the per-column partials

@@ -110,6 +110,13 @@ hipError_t launch_fused_x3_shape(int shape, int variant, const FusedArgs& a, int
 hipError_t launch_fused_x3_shape_savep(int shape, int variant, const FusedArgs& a, int grid,
                                        hipStream_t s);
 
+// bf16-operand fused kernel (DLADMM_PREC_BF16 with DLADMM_F_BF16_FUSED, path 7,
+// dladmm_fused_bf16.hip); Ap / Wp hold one bf16x8 fragment per k-step in the k order of the
+// lane's state registers (pack_frags_kernel, bf16 = 2)
+bool bf16_fused_supports(int variant);
+hipError_t launch_fused_bf16_shape(int shape, int variant, const FusedArgs& a, int grid,
+                                   hipStream_t s);
+
 }  // namespace dladmm
 
 namespace dladmm {

@@ -29,7 +29,7 @@ class ForwardResult:
     P: Optional[torch.Tensor] = None  # [K, m, B] A Z_k per layer (want_P: training forwards)
     path: int = 0  # dladmm_fwd_path: the kernel path that ran (1 fused, 2 per-layer, 3 bf16
                    # tiles, 4 fused split-f16, 5 fused row-split, 6 its four-workgroup
-                   # form; 0 = nothing launched)
+                   # form, 7 fused bf16; 0 = nothing launched)
     flags: int = 0  # the plan options (dladmm_flags) the forward ran with; its backward keeps them
     p0_reused: bool = False  # the load-P0 form ran: A Z0 and the packed A came from a PrologueCache
 
@@ -39,14 +39,17 @@ _FLAG_NAMES = {"per_layer": _lib.F_PER_LAYER, "bf16_wide": _lib.F_BF16_WIDE,
                "bwd_per_layer": _lib.F_BWD_PER_LAYER, "bwd_unfused": _lib.F_BWD_UNFUSED,
                "bwd_no_zmask": _lib.F_BWD_NO_ZMASK, "wgrad_f32": _lib.F_WGRAD_F32,
                "no_rowsplit": _lib.F_NO_ROWSPLIT, "no_xsplit": _lib.F_NO_XSPLIT,
-               "rowsplit_rows": _lib.F_ROWSPLIT_ROWP}
+               "rowsplit_rows": _lib.F_ROWSPLIT_ROWP,
+               "bf16_fused": _lib.F_BF16_FUSED}
 
 
 @contextlib.contextmanager
 def plan_flags(**opts):
     """Plan options (include/dladmm.h enum dladmm_flags) for every forward / backward call made
     inside the block, e.g. `with plan_flags(per_layer=True): net(X)` runs the per-layer kernels
-    where the fused kernel would fit.  They select kernels, never arithmetic; the C ABI receives
+    where the fused kernel would fit; `plan_flags(bf16_fused=True)` runs a precision="bf16"
+    forward of V1 / V4 / V5 / V6 at m <= 256, n <= 512 as the one-launch register-resident bf16
+    kernel (path 7) instead of the per-layer tile kernels.  They select kernels, never arithmetic; the C ABI receives
     them in dladmm_fwd_desc.flags (the library reads no environment).  Nested blocks add to the
     enclosing block's flags; a False value clears that flag.  A backward keeps the options its
     forward ran with (ForwardResult.flags; autograd runs backwards on worker threads, outside

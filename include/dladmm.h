@@ -157,7 +157,9 @@ typedef struct dladmm_fwd_desc {
          run PREC_F32;
        DLADMM_PREC_BF16 (BASELINE config 5: A, W_k and the state operands Var / Z_k rounded to bf16
          for the MFMAs, fp32 accumulation, every elementwise update -- shrinks, E, dual L, T -- in
-         fp32).  bf16 runs on the per-layer kernels (path 3). */
+         fp32).  bf16 runs on the per-layer tile kernels (path 3); with DLADMM_F_BF16_FUSED, V1 /
+         V4 / V5 / V6 at m <= 256, n <= 512 run the one-launch register-resident kernel (path
+         7: the same operand rounding, another accumulation order). */
   int32_t precision;
   /* plan options, a bitwise OR of enum dladmm_flags (0 = the default plan).  They change which
      kernels run -- never the arithmetic a kernel performs -- and the descriptor is the whole
@@ -229,7 +231,14 @@ enum dladmm_flags {
   DLADMM_F_ELZ = 2048,
   /* With DLADMM_F_ELZ and P != NULL ([layers + 1][m][ld_out]): after the last step also form
      P[layers] = A Z[layers - 1] -- what the newS safeguard norm needs (dladmm_safeguard_news_f32) */
-  DLADMM_F_ELZ_TAIL = 4096
+  DLADMM_F_ELZ_TAIL = 4096,
+  /* DLADMM_PREC_BF16 only: the whole K-layer forward as one launch of the register-resident
+     bf16 kernel (path 7) for V1 / V4 / V5 / V6 at m <= 256, n <= 512, where batch, ld_out and
+     ld_z0 are multiples of 4 and Z0 and the outputs are 16-byte aligned (the kernel stores rows
+     in 16-byte pieces), and DLADMM_F_PER_LAYER is not set.  Everything else -- V2 / V3, larger
+     shapes, other layouts, the flag not set -- stays on path 3.  Inference only; P is not
+     written.  No effect with any other precision. */
+  DLADMM_F_BF16_FUSED = 8192
 };
 
 /* ABI version the library was built with. */
@@ -246,7 +255,8 @@ size_t dladmm_fwd_workspace_bytes(const dladmm_fwd_desc* d);
    DLADMM_F_ROWSPLIT_ROWP) at m <= 256, n <= 512 (and m > 64 or n > 256) -- the same arithmetic as path 1, bit for bit (the fused
    objective's per-column sums: to fp32 rounding), 6 = the same split over four workgroups per
    16 columns (16 waves; the column state handed between them through the workspace once per
-   product) where that grid fits one workgroup per CU (B <= 1,024 on 256 CUs), also bit for bit;
+   product) where that grid fits one workgroup per CU (B <= 1,024 on 256 CUs), also bit for bit,
+   7 = fused kernel on bf16 operands (DLADMM_PREC_BF16 with DLADMM_F_BF16_FUSED);
    <0 = DLADMM_E_* error.  Host-only: no device work. */
 int dladmm_fwd_path(const dladmm_fwd_desc* d);
 
