@@ -28,6 +28,7 @@ F_P0_REUSE = 1024    # path 1, fp32: read them from the workspace a F_P0_SAVE ca
 F_ELZ = 2048         # `layers` steps E, L, Z from (Z0, E0, L0): the newS loop's entry (paths 1, 5)
 F_ELZ_TAIL = 4096    # with F_ELZ and P: also P[layers] = A Z[layers - 1]
 F_BF16_FUSED = 8192  # precision bf16: the one-launch register-resident forward (path 7)
+F_BF16_FUSED_ROWP = 16384  # with F_BF16_FUSED: path 7 also for the per-row variants V2 / V3
 # enum dladmm_variant
 V1_LENA, V2_LTHETA, V3_FULL, V4_SCALAR, V5_TIED, V6_LASSO = 1, 2, 3, 4, 5, 6
 V7_SCALAR_V1E = 7    # the V1 E-step with scalar parameters and a step (the newS KM iteration)

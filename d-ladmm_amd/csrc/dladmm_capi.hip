@@ -520,9 +520,12 @@ inline int make_plan(const dladmm_fwd_desc* d, Plan* p) {
     return 0;
   }
   // bf16 fused kernel (opt-in): register-resident shapes, V1 / V4 / V5 / V6, the 16-byte row
-  // layout of its tile stores; every other bf16 call keeps the tile kernels (path 3)
+  // layout of its tile stores; every other bf16 call keeps the tile kernels (path 3).  V2 / V3
+  // take it only under DLADMM_F_BF16_FUSED_ROWP (the row table is read in place, dword by dword).
+  const bool bf16_rows = (d->flags & DLADMM_F_BF16_FUSED_ROWP) &&
+                         bf16_fused_supports_rows(d->variant);
   if (s >= 0 && fits_32bit(d) && !force_layered && bf16 && (d->flags & DLADMM_F_BF16_FUSED) &&
-      bf16_fused_supports(d->variant) && x3_layout_ok(d)) {
+      (bf16_fused_supports(d->variant) || bf16_rows) && x3_layout_ok(d)) {
     p->path = 7;
     p->shape = s < 1 ? 1 : s;  // the kernel's smallest instantiation is shape 1
     p->MP = kShapeMP[p->shape];
@@ -831,6 +834,7 @@ inline int run_fused_bf16(const dladmm_fwd_desc* d, const Plan& p, char* ws, hip
   a.Ap = Ap; a.Wp = Wp;
   a.wstep = shared ? 0 : 1;
   a.scal = d->scalar_params;
+  a.rowp = d->row_params; a.rstride = d->row_stride;  // V2 / V3: read in place, no workspace
   a.Zo = d->Z; a.Eo = d->E; a.Lo = d->L; a.To = d->T; a.ldo = d->ld_out;
   a.lossp = (float*)(ws + p.off_loss);
   if (d->variant == DLADMM_V1_LENA) {

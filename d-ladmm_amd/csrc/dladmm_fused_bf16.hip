@@ -9,6 +9,11 @@ bool bf16_fused_supports(int variant) {
          variant == DLADMM_V6_LASSO || variant == DLADMM_V1_LENA;
 }
 
+// the per-row models (PK_ROW instantiations): only under DLADMM_F_BF16_FUSED_ROWP
+bool bf16_fused_supports_rows(int variant) {
+  return variant == DLADMM_V2_LTHETA || variant == DLADMM_V3_FULL;
+}
+
 // Shapes 1 and 2, as the split-f16 kernel: the C ABI runs shape-0 problems on shape 1 (zero
 // padding is exact).
 hipError_t launch_fused_bf16_shape(int shape, int variant, const FusedArgs& a, int grid,

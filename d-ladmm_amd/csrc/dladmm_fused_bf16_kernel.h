@@ -36,6 +36,12 @@
 //     dwordx4 store per lane.  Every step issues the same VM operations in every pass of its
 //     type (a pass that returns nothing stores through an empty buffer range), which is what
 //     makes the barrier's count static.
+//   * Per-row parameters (V2 / V3, PK_ROW; DLADMM_F_BF16_FUSED_ROWP).  No LDS is left for the
+//     fp32 fused kernel's row table, so an epilogue row's values come straight from a.rowp by
+//     dword buffer loads into a register ring a few rows deep, each row reloading its own slot
+//     for a later row; the loads are counted in Sched::ops1 / ops2 like V1's.  V3 at 256 x 512
+//     (kTight) also holds E: a one-row ring, two fragments in rotation, and the lane index formed
+//     again at its once-per-pass uses bring it to zero scratch.
 #pragma once
 
 #include "dladmm_common.h"
@@ -65,6 +71,9 @@ __device__ __forceinline__ bf16x8 cvt8(const float (&a)[4], const float (&b)[4])
 }
 __device__ __forceinline__ void pin_agpr_b(bf16x8& b) { asm("" : "+a"(b)); }
 
+// per-row models: epilogue rows (one per KS / 4 steps) that cover 8 steps, the row-table look-ahead
+constexpr int rp_depth(int KS) { return KS >= 16 ? 2 : 32 / KS; }
+
 __device__ __forceinline__ void bstore4(rsrc_t r, uint32_t voff, uint32_t soff, f32x4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(bi32x4, v), r, (int)voff, (int)soff, 0);
 }
@@ -74,7 +83,11 @@ __device__ __forceinline__ void bstore4(rsrc_t r, uint32_t voff, uint32_t soff, 
 // tiles are read back one step after row 3 and stored one step after that.  "Step" counts on
 // past the pass's last MFMA step (the tail runs the same actions without MFMAs).
 // PF: V1's per-element beta loads per epilogue row (3), issued one block ahead of the rows.
-template <int MB, int NB, int KS1, int KS2, int PF>
+// RP: the per-row models' (V2 / V3) row-table loads per G2 epilogue row (4 / 5; a G1 row: one,
+// theta_z).  The epilogue rows of a pass form one sequence q = 4 b + r; row q, once it has
+// consumed its ring slot, reloads the slot for row q + DQ (DQ1 / DQ2: the ring depth of G1 / G2 in
+// rows).
+template <int MB, int NB, int KS1, int KS2, int PF, int RP = 0, int DQ1 = 0, int DQ2 = 0>
 struct Sched {
   static constexpr int ST = NB * KS1;
   static constexpr int row_step(int r, int KS) { return (r * KS) / 4; }
@@ -90,12 +103,24 @@ struct Sched {
     return (u >= KS && u % KS == 0) ? u / KS - 1 : -1;
   }
   static constexpr int st_block(int t, int KS) { return rb_block(t - 1, KS); }
-  // VM operations a step body issues (t < ST): G1 the Z tile; G2 the E, L, T tiles and the
-  // beta loads of block t / KS2 + 1
-  static constexpr int ops1(int t) { return st_block(t, KS1) >= 0 ? 1 : 0; }
+  // epilogue rows of step t (block t / KS - 1's) that reload their row-table slots: those whose
+  // row q + DQ is still a row of the pass
+  static constexpr int rp_rows(int t, int KS, int NBLK, int DQ) {
+    int c = 0;
+    for (int r = 0; r < 4; ++r)
+      c += (RP && t / KS >= 1 && row_step(r, KS) == t % KS && 4 * (t / KS - 1) + r + DQ < 4 * NBLK)
+               ? 1 : 0;
+    return c;
+  }
+  // VM operations a step body issues (t < ST): G1 the Z tile and the rows' theta_z loads; G2 the
+  // E, L, T tiles, the beta loads of block t / KS2 + 1 and the rows' row-table loads
+  static constexpr int ops1(int t) {
+    return (st_block(t, KS1) >= 0 ? 1 : 0) + rp_rows(t, KS1, NB, DQ1);
+  }
   static constexpr int ops2(int t) {
     return (st_block(t, KS2) >= 0 ? 3 : 0) +
-           ((PF && t / KS2 + 1 < MB) ? PF * rows_at(t % KS2, KS2) : 0);
+           ((PF && t / KS2 + 1 < MB) ? PF * rows_at(t % KS2, KS2) : 0) +
+           RP * rp_rows(t, KS2, MB, DQ2);
   }
   // The ring barrier in the head of step T (chunk ch = T / kSPC) waits for chunk ch + 1, whose
   // DMA group went out in the head of step T - (kSlots - 1) kSPC.  Younger than it: the bodies
@@ -130,7 +155,10 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
   static_assert(MB % 2 == 0 && NB % 2 == 0 && KS1 >= 2, "k-steps cover two 16-row blocks");
   static_assert(ST % kSPC == 0, "whole chunks per pass");
   constexpr int NCH = ST / kSPC;
-  constexpr int R = 4;      // fragment register rotation; divides ST: every pass starts at 0
+  // V3 at 256 x 512 (per-row parameters and a resident E): the tightest register budget
+  constexpr bool kTight = PKIND == PK_ROW && EMODE == EM_VVAR && MP == 256;
+  // fragment register rotation; divides ST: every pass starts at 0
+  constexpr int R = kTight ? 2 : 4;
   constexpr int D = R - 1;  // fragment read-ahead (steps)
   static_assert(ST % R == 0 && kSPC >= D + 1, "rotation");
   constexpr int SLOT_F4 = kSPC * 64;
@@ -138,10 +166,19 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
   constexpr int X_F4 = kWaves * MB * 64;
   constexpr int STG_F4 = kWaves * 4 * 64;  // per wave 4 output tiles of 16 x 16 floats
   static_assert((RING_F4 + X_F4 + STG_F4) * 16 <= 160 * 1024, "LDS budget");
-  static_assert(PKIND == PK_SCALAR || PKIND == PK_S1 || (PKIND == PK_ELEM && EMODE == EM_V1),
-                "bf16 fused path: scalar-parameter variants and V1's per-sample betas");
+  static_assert(PKIND == PK_SCALAR || PKIND == PK_S1 || (PKIND == PK_ELEM && EMODE == EM_V1) ||
+                    (PKIND == PK_ROW && (EMODE == EM_V1 || EMODE == EM_VVAR)),
+                "bf16 fused path: scalar-parameter variants, V1's per-sample betas, V2 / V3's rows");
   constexpr bool kElem = PKIND == PK_ELEM;
-  using S = Sched<MB, NB, KS1, KS2, kElem ? 3 : 0>;
+  constexpr bool kRow = PKIND == PK_ROW;
+  // per-row models: beta2, beta3, beta1 of the next layer, theta_e, and V3's ss2
+  constexpr int RP = kRow ? (EMODE == EM_VVAR ? 5 : 4) : 0;
+  // their ring depths in rows: a value is loaded at least 8 steps ahead of its row (V3 at
+  // 256 x 512, which also keeps E resident: 4 steps, the depth its registers leave room for)
+  constexpr int DQ1 = kRow ? rp_depth(KS1) : 0;
+  constexpr int DQ2 = kRow ? ((EMODE == EM_VVAR && MP == 256) ? 1 : rp_depth(KS2)) : 0;
+  using S = Sched<MB, NB, KS1, KS2, kElem ? 3 : 0, RP, DQ1, DQ2>;
+  static_assert(DQ1 <= 4 * NB && DQ2 <= 4 * MB, "row-table look-ahead within a pass");
   constexpr int S31 = S::s3(KS1), S32 = S::s3(KS2);
   static_assert(S32 + 1 < KS2, "G2: X rows read after the block's last row");
   __shared__ f32x4 smem[RING_F4 + X_F4 + STG_F4];
@@ -253,11 +290,54 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
   const uint32_t mbytes = (uint32_t)(m * a.ldo * 4);
   SWalk zw{0u, (uint32_t)(a.ldo * 4)}, mw{0u, (uint32_t)(a.ldo * 4)};
 
+  // ---------------------------------------------------------------- per-row parameters (V2 / V3)
+  // Layer k's slot s of a.rowp ([K][8][rstride]) holds one value per row.  They travel as V1's
+  // per-sample betas do: one dword load per row and parameter straight into a register ring (no
+  // LDS: the weight ring, the X rows and the tiles fill it) -- G2's pr[q % DQ2][p], G1's
+  // pz[q % DQ1] for row q = 4 b + r of the pass; the two rings are never live together.  An
+  // epilogue row reloads its own slot for row q + DQ right after reading it, so the ring is DQ
+  // rows deep and needs no slot beside those in use.  Each slot has a resource of its
+  // own that ends at the slot's true length (m; n for theta_z), so the rows of the padding read 0
+  // -- and stay exactly 0: with Z = q = 0, S(0, th) = 0 for every th; E = S(0 - ss2 0, th) = 0,
+  // T = 0, L = 0 + b3 0, Var = 0 (dladmm_step.h).  The empty asm after a row's loads keeps the
+  // compiler from merging the loads of two rows (adjacent dwords) into one: the ring barrier's
+  // count (Sched::ops1 / ops2) is per load.
+  enum { RP_B2 = 0, RP_B3 = 1, RP_B1N = 2, RP_THE = 3, RP_SS2 = 4 };
+  const uint32_t vrow = (uint32_t)(16 * g);
+  auto row_rsrc = [&](int k, int slot, int rows) -> rsrc_t {
+    return mkrsrc(a.rowp + ((int64_t)k * DLADMM_NSCALAR + slot) * a.rstride, (uint32_t)(rows * 4));
+  };
+  float pz[kRow ? DQ1 : 1];
+  float pr[kRow ? DQ2 : 1][kRow ? RP : 1];
+  rsrc_t rrz = mkrsrc(nullptr, 0u);
+  rsrc_t rrp[kRow ? RP : 1];
+  // row q of the pass, if the pass has it
+  auto rp_row1 = [&](auto Q_) {
+    constexpr int q = decltype(Q_)::value;
+    if constexpr (kRow && q < 4 * NB) {
+      pz[q % DQ1] = bload(rrz, vrow + (uint32_t)(64 * (q / 4) + 4 * (q % 4)));
+      asm volatile("");
+    }
+  };
+  auto rp_row2 = [&](auto Q_) {
+    constexpr int q = decltype(Q_)::value;
+    if constexpr (kRow && q < 4 * MB) {
+      static_for<RP>([&](auto P_) {
+        constexpr int p = decltype(P_)::value;
+        pr[q % DQ2][p] = bload(rrp[p], vrow + (uint32_t)(64 * (q / 4) + 4 * (q % 4)));
+      });
+      asm volatile("");
+    }
+  };
+
   // ---------------------------------------------------------------- epilogue rows
   // G1 block b, row r of layer k: Z_k = S(Z_{k-1} + [s1] q, theta_z), q = -W_k Var (the packed
   // weights are negated), on the resident fp32 Z (main_lena.py:86)
   auto epi1_row = [&](const LayerP& P, int b, int r, float q) {
-    const float z = z_step<PKIND>(Zr[b][r], q, P.s1, [&] { return P.thz; });
+    const float z = z_step<PKIND>(Zr[b][r], q, P.s1, [&]() -> ShrinkP {
+      if constexpr (kRow) return shrink_params(pz[(4 * b + r) % DQ1]);
+      else return P.thz;
+    });
     Zr[b][r] = z;
     pin_agpr(Zr[b][r]);
     stage(0, r, z);
@@ -275,9 +355,26 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
       b3 = pb[b % 3][0][r];
       b2 = pb[b % 3][1][r];
       b1n = pb[b % 3][2][r];
+    } else if constexpr (kRow) {
+      // every value counts as used, also in the prologue, whose rows need beta1 only: a load the
+      // compiler dropped there would be missing from the ring barrier's count
+#pragma unroll
+      for (int p = 0; p < RP; ++p) asm volatile("" : "+v"(pr[(4 * b + r) % DQ2][p]));
+      b2 = pr[(4 * b + r) % DQ2][RP_B2];
+      b3 = pr[(4 * b + r) % DQ2][RP_B3];
+      b1n = pr[(4 * b + r) % DQ2][RP_B1N];
     }
-    const StepOut s = el_step<EMODE>(Pv, x, Er[b][r], Lr[b][r], b2, b3, P.ss2b, pro,
-                                     [&] { return P.ss2; }, [&] { return P.the; });
+    // per-row step and threshold: a float threshold takes the literal shrink form (dladmm_step.h)
+    const StepOut s = el_step<EMODE>(
+        Pv, x, Er[b][r], Lr[b][r], b2, b3, P.ss2b, pro,
+        [&] {
+          if constexpr (kRow && EMODE == EM_VVAR) return pr[(4 * b + r) % DQ2][RP_SS2];
+          else return P.ss2;
+        },
+        [&] {
+          if constexpr (kRow) return pr[(4 * b + r) % DQ2][RP_THE];
+          else return P.the;
+        });
     Er[b][r] = s.e;
     Lr[b][r] = s.l;
     stage(1, r, s.e);
@@ -289,10 +386,32 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
     asm volatile("" : "+v"(fit));
     vn[b & 1][r] = s.var(b1n);  // Var of the next layer (main_lena.py:85)
   };
+  // kTight: the lane index formed again where a once-per-pass action needs it (the volatile asm
+  // keeps it from being hoisted), so that no lane-derived address lives across the passes
+  auto lane_here = [&]() -> int {
+    if constexpr (kTight) {
+      int z = 0;
+      asm volatile("" : "+v"(z));
+      return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z));
+    } else {
+      return lane;
+    }
+  };
+  // col_sum (dladmm_common.h) with the lane index passed in: the same two exchanges and adds
+  auto col_sum_at = [&](float v, int ln) -> float {
+    if constexpr (kTight) {
+      v += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((ln ^ 16) << 2, __builtin_bit_cast(int, v)));
+      v += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((ln ^ 32) << 2, __builtin_bit_cast(int, v)));
+      return v;
+    } else {
+      return col_sum(v);
+    }
+  };
   auto flush_loss = [&](int k) {
     if (lossz && k >= 0) {
-      const float rs = col_sum(regsum);
-      const float fs = LQ ? 0.5f * col_sum(fit) : col_sum(fit);
+      const int ln = lane_here();
+      const float rs = col_sum_at(regsum, ln);
+      const float fs = LQ ? 0.5f * col_sum_at(fit, ln) : col_sum_at(fit, ln);
       if (g == 0) {
         a.lossp[(int64_t)(2 * k + 0) * a.ldl + col] = rs;
         a.lossp[(int64_t)(2 * k + 1) * a.ldl + col] = fs;
@@ -350,7 +469,10 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
     if constexpr (ib >= 0 && ib < NB) {
       static_for<4>([&](auto R_) {
         constexpr int r = decltype(R_)::value;
-        if constexpr (S::row_step(r, KS1) == s) epi1_row(P, ib, r, qp[r]);
+        if constexpr (S::row_step(r, KS1) == s) {
+          epi1_row(P, ib, r, qp[r]);
+          rp_row1(std::integral_constant<int, 4 * ib + r + DQ1>{});
+        }
       });
       // blocks ib - 1, ib complete: the B operand of G2's k-step ib / 2
       if constexpr ((ib & 1) && s == S31) {
@@ -362,6 +484,11 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
   auto g1_pass = [&](int k, const LayerP& P, rsrc_t rzo) {
     const int gi = 2 * k + 1;
     zw.reset();
+    if constexpr (kRow) {
+      rrz = row_rsrc(k, DLADMM_P_THETA_Z, n);
+      // the first DQ1 rows' thresholds, ahead of the pass (younger than every group waited for)
+      static_for<DQ1>([&](auto Q_) { rp_row1(Q_); });
+    }
     static_for<NB>([&](auto IB_) {
       constexpr int ib = decltype(IB_)::value;
       f32x4 acc = zero4;
@@ -416,7 +543,10 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
     if constexpr (ib >= 0 && ib < MB) {
       static_for<4>([&](auto R_) {
         constexpr int r = decltype(R_)::value;
-        if constexpr (S::row_step(r, KS2) == s) epi2_row(P, PRO, ib, r, qp[r], xv[r]);
+        if constexpr (S::row_step(r, KS2) == s) {
+          epi2_row(P, PRO, ib, r, qp[r], xv[r]);
+          rp_row2(std::integral_constant<int, 4 * ib + r + DQ2>{});
+        }
       });
       if constexpr ((ib & 1) && s == S32) {
         Vpk[ib / 2] = cvt8(vn[0], vn[1]);
@@ -424,7 +554,8 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
       }
     }
     // X rows of block ib + 1 (its rows run in the next block's steps), once row 3 has used xv
-    if constexpr (s == S32 + 1 && ib + 1 >= 0 && ib + 1 < MB) xv = xs[(w * MB + ib + 1) * 64 + lane];
+    if constexpr (s == S32 + 1 && ib + 1 >= 0 && ib + 1 < MB)
+      xv = xs[(w * MB + ib + 1) * 64 + lane_here()];
   };
   auto g2_pass = [&](auto PRO_, int k, const LayerP& P, const OutR& O) {
     constexpr bool PRO = decltype(PRO_)::value;
@@ -443,7 +574,19 @@ __global__ __launch_bounds__(256, 1) void bf16_fused_kernel(const FusedArgs a) {
       bw.reset();
       static_for<4>([&](auto R_) { pf_row(std::integral_constant<int, 0>{}, R_); });
     }
-    xv = xs[(w * MB) * 64 + lane];
+    if constexpr (kRow) {
+      // layer k's slots (the prologue: layer 0's, used for Var_0 only) and beta1 of layer k + 1,
+      // clamped at the last layer: that load is issued all the same, its Var feeds nothing
+      const int kk = k < 0 ? 0 : k;
+      const int kn = k < 0 ? 0 : (k + 1 < K ? k + 1 : k);
+      rrp[RP_B2] = row_rsrc(kk, DLADMM_P_BETA2, m);
+      rrp[RP_B3] = row_rsrc(kk, DLADMM_P_BETA3, m);  // V2's table holds beta1 there
+      rrp[RP_B1N] = row_rsrc(kn, DLADMM_P_BETA1, m);
+      rrp[RP_THE] = row_rsrc(kk, DLADMM_P_THETA_E, m);
+      if constexpr (RP > RP_SS2) rrp[RP_SS2] = row_rsrc(kk, DLADMM_P_SS2, m);
+      static_for<DQ2>([&](auto Q_) { rp_row2(Q_); });
+    }
+    xv = xs[(w * MB) * 64 + lane_here()];
     static_for<MB>([&](auto IB_) {
       constexpr int ib = decltype(IB_)::value;
       f32x4 acc = zero4;
@@ -511,6 +654,8 @@ hipError_t dispatch_bf16_variant(int variant, const FusedArgs& a, int grid, hipS
     case DLADMM_V5_TIED: return launch_bf16<MP, NP, EM_VVAR, PK_S1>(a, grid, s);
     case DLADMM_V6_LASSO: return launch_bf16<MP, NP, EM_LASSO, PK_SCALAR>(a, grid, s);
     case DLADMM_V1_LENA: return launch_bf16<MP, NP, EM_V1, PK_ELEM>(a, grid, s);
+    case DLADMM_V2_LTHETA: return launch_bf16<MP, NP, EM_V1, PK_ROW>(a, grid, s);
+    case DLADMM_V3_FULL: return launch_bf16<MP, NP, EM_VVAR, PK_ROW>(a, grid, s);
   }
   return hipErrorInvalidValue;
 }

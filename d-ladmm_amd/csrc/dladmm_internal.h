@@ -112,8 +112,11 @@ hipError_t launch_fused_x3_shape_savep(int shape, int variant, const FusedArgs& 
 
 // bf16-operand fused kernel (DLADMM_PREC_BF16 with DLADMM_F_BF16_FUSED, path 7,
 // dladmm_fused_bf16.hip); Ap / Wp hold one bf16x8 fragment per k-step in the k order of the
-// lane's state registers (pack_frags_kernel, bf16 = 2)
+// lane's state registers (pack_frags_kernel, bf16 = 2).  bf16_fused_supports_rows: V2 / V3, which
+// the plan gives it only under DLADMM_F_BF16_FUSED_ROWP; they read a.rowp in place (dword loads,
+// any rstride)
 bool bf16_fused_supports(int variant);
+bool bf16_fused_supports_rows(int variant);
 hipError_t launch_fused_bf16_shape(int shape, int variant, const FusedArgs& a, int grid,
                                    hipStream_t s);
 

@@ -40,7 +40,8 @@ _FLAG_NAMES = {"per_layer": _lib.F_PER_LAYER, "bf16_wide": _lib.F_BF16_WIDE,
                "bwd_no_zmask": _lib.F_BWD_NO_ZMASK, "wgrad_f32": _lib.F_WGRAD_F32,
                "no_rowsplit": _lib.F_NO_ROWSPLIT, "no_xsplit": _lib.F_NO_XSPLIT,
                "rowsplit_rows": _lib.F_ROWSPLIT_ROWP,
-               "bf16_fused": _lib.F_BF16_FUSED}
+               "bf16_fused": _lib.F_BF16_FUSED,
+               "bf16_fused_rows": _lib.F_BF16_FUSED_ROWP}
 
 
 @contextlib.contextmanager
@@ -49,7 +50,9 @@ def plan_flags(**opts):
     inside the block, e.g. `with plan_flags(per_layer=True): net(X)` runs the per-layer kernels
     where the fused kernel would fit; `plan_flags(bf16_fused=True)` runs a precision="bf16"
     forward of V1 / V4 / V5 / V6 at m <= 256, n <= 512 as the one-launch register-resident bf16
-    kernel (path 7) instead of the per-layer tile kernels.  They select kernels, never arithmetic; the C ABI receives
+    kernel (path 7) instead of the per-layer tile kernels, and with `bf16_fused_rows=True` beside
+    it the per-row models V2 / V3 (DLADMMNetLTheta, DLADMMNetFull) too.
+    They select kernels, never arithmetic; the C ABI receives
     them in dladmm_fwd_desc.flags (the library reads no environment).  Nested blocks add to the
     enclosing block's flags; a False value clears that flag.  A backward keeps the options its
     forward ran with (ForwardResult.flags; autograd runs backwards on worker threads, outside

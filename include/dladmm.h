@@ -158,8 +158,9 @@ typedef struct dladmm_fwd_desc {
        DLADMM_PREC_BF16 (BASELINE config 5: A, W_k and the state operands Var / Z_k rounded to bf16
          for the MFMAs, fp32 accumulation, every elementwise update -- shrinks, E, dual L, T -- in
          fp32).  bf16 runs on the per-layer tile kernels (path 3); with DLADMM_F_BF16_FUSED, V1 /
-         V4 / V5 / V6 at m <= 256, n <= 512 run the one-launch register-resident kernel (path
-         7: the same operand rounding, another accumulation order). */
+         V4 / V5 / V6 (V2 / V3 with DLADMM_F_BF16_FUSED_ROWP as well) at m <= 256, n <= 512 run
+         the one-launch register-resident kernel (path 7: the same operand rounding, another
+         accumulation order). */
   int32_t precision;
   /* plan options, a bitwise OR of enum dladmm_flags (0 = the default plan).  They change which
      kernels run -- never the arithmetic a kernel performs -- and the descriptor is the whole
@@ -238,7 +239,13 @@ enum dladmm_flags {
      in 16-byte pieces), and DLADMM_F_PER_LAYER is not set.  Everything else -- V2 / V3, larger
      shapes, other layouts, the flag not set -- stays on path 3.  Inference only; P is not
      written.  No effect with any other precision. */
-  DLADMM_F_BF16_FUSED = 8192
+  DLADMM_F_BF16_FUSED = 8192,
+  /* With DLADMM_F_BF16_FUSED: path 7 also for the per-row-parameter variants V2 / V3, which keep
+     path 3 without it (as DLADMM_F_ROWSPLIT_ROWP does for paths 5 / 6), under the conditions
+     above.  The kernel reads row_params in place, one dword per row and parameter (any
+     row_stride).  Same workspace as the other variants' path 7.  No effect alone, on any other
+     variant, or with any other precision. */
+  DLADMM_F_BF16_FUSED_ROWP = 16384
 };
 
 /* ABI version the library was built with. */
@@ -256,7 +263,8 @@ size_t dladmm_fwd_workspace_bytes(const dladmm_fwd_desc* d);
    objective's per-column sums: to fp32 rounding), 6 = the same split over four workgroups per
    16 columns (16 waves; the column state handed between them through the workspace once per
    product) where that grid fits one workgroup per CU (B <= 1,024 on 256 CUs), also bit for bit,
-   7 = fused kernel on bf16 operands (DLADMM_PREC_BF16 with DLADMM_F_BF16_FUSED);
+   7 = fused kernel on bf16 operands (DLADMM_PREC_BF16 with DLADMM_F_BF16_FUSED; V2 / V3 also
+   need DLADMM_F_BF16_FUSED_ROWP);
    <0 = DLADMM_E_* error.  Host-only: no device work. */
 int dladmm_fwd_path(const dladmm_fwd_desc* d);
 
